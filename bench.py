@@ -13,7 +13,11 @@ by torchrun (WORLD_SIZE set) or as ``bench.py --gpus N``, which spawns the N
 ranks itself (fresh processes, before any GPU call) and fails when fewer than
 N GPUs are visible.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the
+steps and prints that line (``--dump-outputs DIR`` also writes what the last
+timed step computed).  Everything that takes runs of its own -- the host
+output conversion, the design-point line, the CPU baseline, the sweep's ALU
+roofline -- is behind ``--full``.
 """
 from __future__ import annotations
 
@@ -61,8 +65,16 @@ def parse():
     ap.add_argument("--size", type=int, default=10000, help="slide is size x size pixels")
     ap.add_argument("--channels", type=int, default=30)
     ap.add_argument("--k", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what is not the headline figure: "
+                         "the reference-format host outputs, the design-point line, the CPU "
+                         "baseline and (with --sweep) the dense pass's ALU roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy "
+                         "(float32 / float64; per-pixel outputs as a fixed, seeded sample)")
     ap.add_argument("--no-design-point", action="store_true",
-                    help="skip the second line on the design-point slide (--mode design, I~17)")
+                    help="with --full: skip the second line on the design-point slide "
+                         "(--mode design, I~17)")
     ap.add_argument("--mode", default="hard", choices=["hard", "easy", "design"],
                     help="synthetic slide: hard (the headline), design (overlapping domains: "
                          "SURVEY 8d's I~17 Lloyd iterations), easy")
@@ -77,10 +89,11 @@ def parse():
     ap.add_argument("--sweep", action="store_true",
                     help="time find_optimal_k (k=2..20) over the prepped rows instead of the "
                          "label pipeline (BASELINE config 4)")
-    ap.add_argument("--cpu-size", type=int, default=2048, help="oracle CPU-baseline slide side")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-size", type=int, default=2048,
+                    help="with --full: oracle CPU-baseline slide side")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-host-outputs", action="store_true",
-                    help="skip the reference-format host outputs after the timed steps (timeline traces)")
+                    help="with --full: skip the reference-format host outputs after the timed steps")
     return ap.parse_args()
 
 
@@ -431,10 +444,64 @@ def host_outputs(lab):
                     "stay in HBM"}
 
 
+DUMP_SAMPLE_PIXELS = 6_000_000  # per-pixel values written by --dump-outputs, over all slides (2 x 4 B each)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(lab, out_dir, sweep, rank, world, n_sl):
+    """``--dump-outputs``: what a caller of the timed step receives from its
+    last run, as ``out_dir/<name>.npy``.  Label pipeline: the fit (centers,
+    inertia, iterations; rank 0), the scaler, and per slide ``s<index>`` (index
+    over all ranks) the tissue IDs and the confidences (float32; -1
+    outside the mask, where the host arrays hold NaN) and the per-domain mean confidences; a slide with
+    more pixels than its share of DUMP_SAMPLE_PIXELS is written at a fixed,
+    seeded sample of flat pixel indices (sorted default_rng(DUMP_SEED) draws,
+    the same for every slide and run; 48 MB of per-pixel values in all).
+    Sweep: the scaled-inertia curve and the chosen k."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a, dtype=np.float64):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    if sweep:
+        if rank == 0:
+            save("scaled_inertia", lab.inertia_curve_["Scaled Inertia"].values)
+            save("best_k", [lab.k])
+        return
+    if rank == 0:
+        save("cluster_centers", lab.kmeans.cluster_centers_)
+        save("inertia", [lab.kmeans.inertia_])
+        save("n_iter", [lab.kmeans.n_iter_])
+        save("scaler_mean", lab.scaler.mean_)
+        save("scaler_scale", lab.scaler.scale_)
+    share = max(DUMP_SAMPLE_PIXELS // (world * n_sl), 1)
+    means = np.asarray(lab.confidence_score_df.values, dtype=np.float64)
+    for i, (labels, conf) in enumerate(zip(lab._labels_dev, lab._conf_dev)):
+        g = rank * n_sl + i
+        labels, conf = labels.reshape(-1), conf.reshape(-1)
+        n = labels.numel()
+        if n > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=share))
+            idx = torch.from_numpy(idx).to(labels.device)
+            labels, conf = labels[idx], conf[idx]
+        # outside the mask the host arrays hold NaN; the files hold -1 there
+        # (no label or confidence is negative), so every written value is
+        # finite and a NaN inside the mask still shows
+        outside = labels < 0
+        save(f"tissue_IDs_s{g}", labels.to(torch.float32).cpu().numpy(), np.float32)
+        c = conf.to(torch.float32)
+        c[outside] = -1.0
+        save(f"confidence_IDs_s{g}", c.cpu().numpy(), np.float32)
+        save(f"domain_confidence_s{g}", np.nan_to_num(means[i], nan=-1.0))  # a domain without pixels: -1
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1:
+        print("bench.py: --steps must be >= 1", file=sys.stderr)
         sys.exit(2)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         if os.environ.get("MW_BENCH_SHARE_GPU") != "1":
@@ -509,6 +576,8 @@ def main():
               file=sys.stderr, flush=True)
     profiling.enable(False)
     prof = profiling.summary()
+    if args.dump_outputs:
+        dump_outputs(lab, args.dump_outputs, args.sweep, rank, world, n_sl)
     t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -592,7 +661,7 @@ def main():
                         "fit_passes": fit_passes, "lloyd_device_ms": pass_ms,
                         "device_ms_per_fit_pass": pass_ms / max(fit_passes, 1),
                         "curve": [float(v) for v in curve["Scaled Inertia"].values]}
-        if world == 1:
+        if args.full and world == 1:
             out["sweep"]["alu_roofline"] = dense_pass_roofline(lab._device_rows())
         out["config"]["workload"] = (f"find_optimal_k k=2..20 over {world} GPU(s) x {n_sl} synthetic "
                                      f"{C}-ch {H}x{W} slide(s) per GPU ({S_glob} rows; "
@@ -624,12 +693,12 @@ def main():
                         "Lloyd pass of the rank's last fit read (its bounds skip the rest), x F x 4 B"})
             out["pipeline_roofline"]["frac_bytes_read"] = (out["pipeline_roofline"]["achieved_bytes_read"]
                                                            / (HBM_PEAK_GBPS * world))
-    if not args.sweep and not args.no_host_outputs:
+    if args.full and not args.sweep and not args.no_host_outputs:
         out["host_outputs"] = host_outputs(lab)
-    if (world == 1 and not args.sweep and args.mode == "hard" and not args.no_design_point
+    if (args.full and world == 1 and not args.sweep and args.mode == "hard" and not args.no_design_point
             and source == "device" and n_sl == 1 and H * W * C * 2 <= 20e9):
         out["design_point"] = design_point(H, W, C, args.k, comm, lab)
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_size, C, args.k, sweep=args.sweep)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -27,7 +27,7 @@ for r in csv.DictReader(open(f)):
         print(f"{n[:60]:60s} {r['Calls']:>5s} {float(r['AverageNs'])/1e3:9.1f} us")
 PY
 for v in 1 0 1 0; do
-  MW_KPP_FOLD=$v timeout -k 10 300 python -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-outputs > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err" || { tail -5 "$OUT/bench_$v.err"; exit 1; }
+  MW_KPP_FOLD=$v timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-outputs > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err" || { tail -5 "$OUT/bench_$v.err"; exit 1; }
   python -c "import json; d=json.load(open('$OUT/bench_$v.json')); print('FOLD=$v', round(d['ms_per_step'],3), 'fit', d['kernels']['kmeans_fit']['mean_ms'], 'design', round(d['design_point']['ms_per_step'],3), d['design_point']['kmeans_fit_ms'])"
 done
 echo "[r6_fold] done"
