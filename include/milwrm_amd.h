@@ -69,6 +69,31 @@ int mw_nz_stats(const void* d_img, int dtype, int64_t n_pix, int C,
 int mw_lognorm(const void* d_img, int dtype, int64_t n_pix, int C,
                const float* d_inv_mean, float pseudoval, float* d_out, void* stream);
 
+/* ---- img.clip / img.scale (MxIF.py:29-92, 330-358) ---------------------------
+ * Exact order statistics of an HWC image by a most-significant-digit-first
+ * radix select (8-bit digits over monotone uint32 keys: 1 pass for u8, 2 for
+ * u16, 4 for fp32; no host synchronisation between the passes).  NaNs are left
+ * out and counted; -0.0 orders equal to +0.0 and is returned as +0.0.
+ * pooled = 0: every channel on its own; pooled = 1: the image as one channel
+ * of n_pix * C elements, without the elements equal to -99999 when
+ * skip_sentinel is set.  h_q: nq percentiles in [0, 100] (host, nq <= 8).
+ * d_out (device, [channels][nq][4] doubles): for numpy's 'linear' rule on the
+ * n kept values, v = q/100 (n-1), the order statistics of rank floor(v) and
+ * min(floor(v)+1, n-1), then n and the NaN count (NaN, NaN, 0, NaNs when
+ * n = 0).  The caller interpolates on the host.  The image must be 16-byte
+ * aligned; C <= 256 per-channel (MW_EUNSUPPORTED above). */
+size_t mw_quantiles_ws_bytes(int C, int nq);
+int mw_quantiles(const void* d_img, int dtype, int64_t n_pix, int C,
+                 int pooled, const double* h_q, int nq, int skip_sentinel,
+                 double* d_out, void* d_ws, void* stream);
+/* Elementwise intensity rescale, fp32 out (may alias an fp32 in).  d_params
+ * (device, [C][5] doubles): lo, hi, omin, omax, mode with mode 0 = the value
+ * itself, 1 = (clip(x, lo, hi) - lo) / (hi - lo) * (omax - omin) + omin,
+ * 2 = clip(x, omin, omax), 3 = (x - lo) / (hi - lo); evaluated in fp64 without
+ * contraction and rounded once to fp32.  NaN stays NaN in modes 0-2. */
+int mw_rescale(const void* d_img, int dtype, int64_t n_pix, int C,
+               const double* d_params, float* d_out, void* stream);
+
 /* ---- img.blurring('gaussian', sigma) (MxIF.py:375-394) ----------------------
  * Separable Gaussian, per channel, edge-replicate ('nearest'), radius r =
  * int(4*sigma+0.5) <= 32, taps h_w[0..2r] (scipy _gaussian_kernel1d).

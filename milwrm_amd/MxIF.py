@@ -26,15 +26,58 @@ def checktype(obj):
 
 def _out_of_scope(name):
     def f(*a, **k):
-        raise NotImplementedError(f"{name} is outside the MI355X hot path (plotting / intensity "
-                                  "utilities); use the reference implementation")
+        raise NotImplementedError(f"{name} is outside the MI355X hot path (plotting / adaptive histogram "
+                                  "equalisation); use the reference implementation")
     f.__name__ = name
     return f
 
 
-clip_values = _out_of_scope("clip_values")
-scale_rgb = _out_of_scope("scale_rgb")
 CLAHE = _out_of_scope("CLAHE")
+
+_CLIP_Q = (0.5, 99.5)  # clip_values' percentiles (MxIF.py:47,57)
+
+
+def _lerp_quantile(a, b, n, q):
+    """numpy's 'linear' percentile ``q`` of ``n`` values from its two order
+    statistics: ``a`` of rank floor(v) and ``b`` of rank min(floor(v) + 1,
+    n - 1), v = q/100 (n - 1).  Float64 on the host; NaN when n = 0."""
+    if n < 1:
+        return float("nan")
+    v = float(q) / 100 * (int(n) - 1)
+    t = v - np.floor(v)
+    a, b = float(a), float(b)
+    d = b - a
+    return float(a + d * t if t < 0.5 else b - d * (1 - t))
+
+
+def _clip_params(vmin, vmax):
+    """rescale_intensity(x, in_range=(vmin, vmax), out_range=np.float32) as a
+    D.rescale row: the output range is [0, 1], or [-1, 1] when vmin < 0."""
+    omin = 0.0 if vmin >= 0 else -1.0
+    mode = D.RESCALE_FLAT if vmin == vmax else D.RESCALE_CLIP
+    return (vmin, vmax, omin, 1.0, mode)
+
+
+def _module_call(image, op, channels):
+    """clip_values / scale_rgb of a host array through a temporary ``img``."""
+    a = np.asarray(image)
+    im = img(a)
+    getattr(im, op)(channels=channels)
+    out = im._dev.cpu().numpy()
+    return out if a.ndim > 2 else out[:, :, 0]
+
+
+def clip_values(image, channels=None):
+    """MxIF.py:29-64 on the device (``img.clip``): float32 in the pooled branch
+    (``channels`` None or a 2-D image), float64 otherwise, as the reference
+    gives for its float64 images."""
+    out = _module_call(image, "clip", channels)
+    return out if channels is None or np.ndim(image) == 2 else out.astype(np.float64)
+
+
+def scale_rgb(image, channels=None):
+    """MxIF.py:67-92 on the device (``img.scale``); float64."""
+    return _module_call(image, "scale", channels).astype(np.float64)
 
 
 class _DeviceMask:
@@ -442,8 +485,71 @@ class img:
         else:
             np.savez_compressed(file, img=self.img, ch=self.ch, mask=self.mask)
 
-    clip = _out_of_scope("img.clip")
-    scale = _out_of_scope("img.scale")
+    # ----------------------------------------------------------- intensity
+    def _intensity(self, channels, select, rows_of):
+        """clip / scale: pending transforms applied, then per round one exact
+        selection (D.quantiles, one host read of its few numbers) and one
+        rescale pass.  ``select(t, pooled)`` queues the selection;
+        ``rows_of(record)`` turns a channel's record into its D.rescale row.
+        A channel listed twice is processed twice, as the reference's loop
+        does."""
+        if getattr(self, "_band", None) is not None:
+            raise NotImplementedError("clip / scale of a row band of a slide: the percentiles are the "
+                                      "whole slide's")
+        t = self._materialize()  # a slide that is not resident: _device()'s MemoryError
+        C = int(t.shape[2])
+        if channels is None or self._ndim == 2:
+            rounds = [None]
+        else:
+            if isinstance(channels, (int, np.integer, str)):
+                channels = (channels,)
+            todo = self._features(list(channels))
+            rounds = []
+            while todo:
+                uniq = list(dict.fromkeys(todo))
+                rounds.append(uniq)
+                for c in uniq:
+                    todo.remove(c)
+        for chs in rounds:
+            params = np.zeros((C, 5), dtype=np.float64)  # mode 0: the value itself
+            if chs is None:
+                params[:] = rows_of(D.d2h(select(t, True))[0])
+            else:
+                st = D.d2h(select(t, False))
+                for c in chs:
+                    params[c] = rows_of(st[c])
+            t = D.rescale(t, params)
+        self._set_device(t)
+        self._xbound = None
+        self._lognorm_host = None
+
+    def clip(self, channels=None):
+        """MxIF.py:330-343 / clip_values (MxIF.py:29-64): rescale to the 0.5 and
+        99.5 percentiles (NaNs left out) as skimage's rescale_intensity(...,
+        out_range=np.float32) does.  ``channels`` None (or a 2-D image): one
+        pair over all channels, elements equal to -99999 left out as well;
+        else a tuple of channel indices (or names), each plane with its own
+        pair, the others unchanged.  The pixels become fp32."""
+        def rows_of(st):
+            n = int(st[0, 2])
+            return _clip_params(_lerp_quantile(st[0, 0], st[0, 1], n, _CLIP_Q[0]),
+                                _lerp_quantile(st[1, 0], st[1, 1], n, _CLIP_Q[1]))
+
+        self._intensity(channels, lambda t, pooled: D.quantiles(t, _CLIP_Q, pooled=pooled,
+                                                                skip_sentinel=pooled), rows_of)
+
+    def scale(self, channels=None):
+        """MxIF.py:345-358 / scale_rgb (MxIF.py:67-92): (x - min) / (max - min),
+        one min / max over everything (``channels`` None or a 2-D image) or per
+        listed plane.  As numpy's min(): a plane holding a NaN becomes NaN, and
+        a constant plane gives 0/0 = NaN.  The pixels become fp32."""
+        def rows_of(st):
+            nan = float("nan")
+            lo, hi = (st[0, 0], st[1, 1]) if st[0, 3] == 0 and st[0, 2] > 0 else (nan, nan)
+            return (lo, hi, 0.0, 1.0, D.RESCALE_SCALE)
+
+        self._intensity(channels, lambda t, pooled: D.quantiles(t, (0.0, 100.0), pooled=pooled), rows_of)
+
     equalize_hist = _out_of_scope("img.equalize_hist")
     show = _out_of_scope("img.show")
     plot_image_histogram = _out_of_scope("img.plot_image_histogram")

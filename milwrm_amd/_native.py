@@ -36,6 +36,9 @@ _PROTOS = {
     "mw_nz_stats_ws_bytes": (c_sz, [c_i64, c_i32]),
     "mw_nz_stats": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mw_lognorm": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
+    "mw_quantiles_ws_bytes": (c_sz, [c_i32, c_i32]),
+    "mw_quantiles": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "mw_rescale": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "mw_blur_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "mw_blur": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mw_block_mean": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

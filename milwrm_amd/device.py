@@ -277,6 +277,48 @@ def lognorm(img: torch.Tensor, inv_mean: torch.Tensor, pseudoval: float, out=Non
     return out
 
 
+def quantiles(img: torch.Tensor, q, pooled: bool = False, skip_sentinel: bool = False) -> torch.Tensor:
+    """Exact order statistics of an HWC image for the percentiles ``q`` (numpy's
+    'linear' rule): a device fp64 tensor [channels, len(q), 4] of the order
+    statistics of rank floor(v) and min(floor(v) + 1, n - 1), v = q/100 (n - 1),
+    the kept count n and the NaN count.  ``pooled``: the image as one channel
+    (``skip_sentinel``: without the elements equal to -99999).  Nothing is
+    synchronised: the caller reads the result when it needs it."""
+    H, W, C = img.shape
+    if not img.is_contiguous():
+        raise ValueError("quantiles: the image must be contiguous")
+    qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    nq = int(qa.size)
+    out = torch.empty((1 if pooled else C, nq, 4), dtype=torch.float64, device=img.device)
+    ws = WS.get("quantiles", N.query("mw_quantiles_ws_bytes", C, max(1, min(nq, 8))))
+    passes = {torch.uint8: 1, torch.int16: 2}.get(img.dtype, 4)
+    with profiling.timed("quantiles", passes * H * W * C * img.element_size()):
+        N.call("mw_quantiles", P(img), dtype_code(img), H * W, C, int(bool(pooled)), qa.ctypes.data, nq,
+               int(bool(skip_sentinel)), P(out), P(ws), stream())
+    return out
+
+
+RESCALE_PASS, RESCALE_CLIP, RESCALE_FLAT, RESCALE_SCALE = 0.0, 1.0, 2.0, 3.0
+
+
+def rescale(img: torch.Tensor, params, out=None) -> torch.Tensor:
+    """Elementwise intensity rescale to fp32.  ``params``: [C, 5] float64 rows
+    (lo, hi, omin, omax, mode), host array or device tensor; mode as the
+    RESCALE_* constants.  ``out`` may be ``img`` itself when it is fp32."""
+    H, W, C = img.shape
+    if not img.is_contiguous():
+        raise ValueError("rescale: the image must be contiguous")
+    if not isinstance(params, torch.Tensor):
+        params = h2d(np.ascontiguousarray(params, dtype=np.float64).reshape(C, 5), img.device)
+    if params.dtype != torch.float64 or tuple(params.shape) != (C, 5) or not params.is_contiguous():
+        raise ValueError(f"rescale: params must be a contiguous float64 [{C}, 5] array")
+    if out is None:
+        out = torch.empty((H, W, C), dtype=torch.float32, device=img.device)
+    with profiling.timed("rescale", H * W * C * (img.element_size() + 4)):
+        N.call("mw_rescale", P(img), dtype_code(img), H * W, C, P(params), P(out), stream())
+    return out
+
+
 def gaussian_taps(sigma: float, truncate: float = 4.0) -> np.ndarray:
     """scipy ``_gaussian_kernel1d`` order 0 (radius int(truncate*sigma+0.5)),
     computed in fp64 then rounded to fp32 for the kernel."""
