@@ -94,6 +94,29 @@ int mw_quantiles(const void* d_img, int dtype, int64_t n_pix, int C,
 int mw_rescale(const void* d_img, int dtype, int64_t n_pix, int C,
                const double* d_params, float* d_out, void* stream);
 
+/* ---- img.blurring('median', size=k) (MxIF.py:395-405 as intended) -----------
+ * Median filter per channel over a size_y x size_x window (rows y - size_y/2
+ * .. y + size_y - 1 - size_y/2, columns likewise; coordinates clamped to the
+ * image, scipy's mode='nearest'): the element of rank (size_y size_x) / 2,
+ * from 0, of the window sorted ascending (the upper median of an even count)
+ * = scipy.ndimage.median_filter(plane, footprint=ones((size_y, size_x)),
+ * mode='nearest').  HWC in; exact: the output is an element of the input
+ * (fp32 subnormals unchanged; windows holding a NaN are undefined).
+ * d_inv_mean == NULL: d_out has the input's dtype.  Otherwise d_out is fp32
+ * and holds mw_lognorm's value of the selected raw element, bit for bit
+ * (selection commutes with the non-decreasing map, so the filter runs on the
+ * compact raw type and writes fp32 once).  Sizes 1..15 per axis: 2x2, 3x3 and
+ * 5x5 take a register selection network, every other size a bitwise rank
+ * search (mw_median_generic: that search for every size;
+ * mw_median_is_network: which of the two mw_median takes).  size < 1 or
+ * d_out == d_img: MW_EINVAL; a size above 15: MW_EUNSUPPORTED (nothing
+ * launched).  No workspace. */
+int mw_median_is_network(int size_y, int size_x);
+int mw_median(const void* d_img, int dtype, int H, int W, int C, int size_y, int size_x,
+              const float* d_inv_mean, float pseudoval, void* d_out, void* stream);
+int mw_median_generic(const void* d_img, int dtype, int H, int W, int C, int size_y, int size_x,
+                      const float* d_inv_mean, float pseudoval, void* d_out, void* stream);
+
 /* ---- img.blurring('gaussian', sigma) (MxIF.py:375-394) ----------------------
  * Separable Gaussian, per channel, edge-replicate ('nearest'), radius r =
  * int(4*sigma+0.5) <= 32, taps h_w[0..2r] (scipy _gaussian_kernel1d).

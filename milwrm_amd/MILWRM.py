@@ -77,8 +77,9 @@ def chooseBestKforKMeansParallel(scaled_data, k_range, n_jobs=-1, comm=None, **k
 # --------------------------------------------------------- MxIF workers
 
 def prep_data_single_sample_mxif(image, use_path, mean, filter_name, sigma, features, fract,
-                                 path_save):
-    """MILWRM.py:172-234 (host-returning form)."""
+                                 path_save, filter_kwargs=None):
+    """MILWRM.py:172-234 (host-returning form).  ``filter_kwargs``: further
+    keywords of ``img.blurring`` (``{"size": k}`` for the median filter)."""
     if use_path:
         if path_save is None:
             raise Exception("Path to save final preprocessed npz files is requird when given path "
@@ -86,7 +87,7 @@ def prep_data_single_sample_mxif(image, use_path, mean, filter_name, sigma, feat
         image_path = image
         image = img.from_npz(image_path + ".npz")
     image.log_normalize(mean=mean)
-    image.blurring(filter_name=filter_name, sigma=sigma)
+    image.blurring(filter_name=filter_name, sigma=sigma, **(filter_kwargs or {}))
     subsampled = image.subsample_pixels(features, fract)
     if use_path:
         file_save = _save_preprocessed(image, image_path, path_save)
@@ -544,15 +545,17 @@ class mxif_labeler(tissue_labeler):
         return {b: est / pixels for b, (est, pixels) in per.items()}
 
     def prep_cluster_data(self, features, filter_name="gaussian", sigma=2, fract=0.2,
-                          path_save=None, comm=None):
+                          path_save=None, comm=None, filter_kwargs=None):
         """MILWRM.py:1672-1745: batch means, per-image lognorm + blur (one
         fused kernel) + subsample gather straight into one HBM row block,
         StandardScaler from device column statistics.  With a sharded
         ``comm`` (milwrm_amd.dist) each rank holds its own slides and the
-        statistics are merged across ranks."""
+        statistics are merged across ranks.  ``filter_kwargs``: further
+        keywords of ``img.blurring`` (``{"size": k}`` for the median filter)."""
         comm = LOCAL_COMM if comm is None else comm
         self._comm = comm
         self._mbl = None
+        fkw = dict(filter_kwargs or {})
         if self._rows is not None or self._cluster_host is not None:
             print("WARNING: overwriting existing cluster data")
             self.cluster_data = None
@@ -572,6 +575,9 @@ class mxif_labeler(tissue_labeler):
             # one slide in row bands over the ranks (milwrm_amd.bands)
             from .bands import prep_banded
 
+            if filter_kwargs is not None:
+                raise NotImplementedError("filter_kwargs on a slide in row bands: the banded pass "
+                                          "runs the gaussian only")
             X, img_stats, xmax = prep_banded(images[0], self.image_df["batch_names"].iloc[0],
                                              means, features, filter_name, sigma, fract, comm)
             self._batch_counts = [int(X.shape[0])]
@@ -590,7 +596,7 @@ class mxif_labeler(tissue_labeler):
         ev0.record()
         if images:
             images[0].log_normalize(mean=means[batches[0]])
-            images[0].blurring(filter_name=filter_name, sigma=sigma)
+            images[0].blurring(filter_name=filter_name, sigma=sigma, **fkw)
         # phase 1: mask ranks → sample counts → one preallocated row block.
         # Only the first image keeps its rank→pixel table (4 bytes per tissue
         # pixel: 5.4 GB per 40k^2 slide); the others are ranked again when
@@ -633,7 +639,7 @@ class mxif_labeler(tissue_labeler):
                 zip(images, self.image_df["batch_names"], ranks, counts)):
             if n_img > 0:
                 im.log_normalize(mean=means[batch])
-                im.blurring(filter_name=filter_name, sigma=sigma)
+                im.blurring(filter_name=filter_name, sigma=sigma, **fkw)
             np.random.seed(16)
             if S:
                 if r2p is None:

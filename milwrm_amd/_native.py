@@ -39,6 +39,9 @@ _PROTOS = {
     "mw_quantiles_ws_bytes": (c_sz, [c_i32, c_i32]),
     "mw_quantiles": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mw_rescale": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "mw_median_is_network": (c_i32, [c_i32, c_i32]),
+    "mw_median": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
+    "mw_median_generic": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     "mw_blur_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "mw_blur": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mw_block_mean": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

@@ -343,6 +343,50 @@ def blur(img: torch.Tensor, sigma: float, inv_mean=None, pseudoval: float = 1.0,
     return out
 
 
+def median_size(size):
+    """``size`` of a median window as (rows, cols): an int or a pair of ints,
+    each at least 1 (ValueError otherwise; no device call)."""
+    def one(v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"median size must be an int or a (rows, cols) pair of ints, got {size!r}")
+        if v < 1:
+            raise ValueError(f"median size must be at least 1, got {size!r}")
+        return int(v)
+
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError(f"median size must be an int or a (rows, cols) pair of ints, got {size!r}")
+        return one(size[0]), one(size[1])
+    return one(size), one(size)
+
+
+def median(img: torch.Tensor, size, inv_mean=None, pseudoval: float = 1.0, out=None,
+           force_generic: bool = False):
+    """Median filter of an HWC image per channel, window ``size`` (an int or
+    (rows, cols), up to 15), edges replicated: scipy's ``median_filter`` with a
+    ones footprint and ``mode='nearest'``, exact.  Without ``inv_mean`` the
+    output has the image's dtype; with it the output is fp32,
+    ``lognorm(median(img))`` bit for bit, written once.  ``force_generic``:
+    the rank search also where a selection network exists (2, 3, 5)."""
+    H, W, C = img.shape
+    sy, sx = median_size(size)
+    if not img.is_contiguous():
+        raise ValueError("median: the image must be contiguous")
+    out_dtype = img.dtype if inv_mean is None else torch.float32
+    if out is None:
+        out = torch.empty((H, W, C), dtype=out_dtype, device=img.device)
+    elif out.dtype != out_dtype or out.shape != img.shape or not out.is_contiguous():
+        raise ValueError(f"median: out must be a contiguous {out_dtype} tensor of shape {tuple(img.shape)}")
+    if inv_mean is not None and (inv_mean.dtype != torch.float32 or inv_mean.numel() != C):
+        raise ValueError(f"median: inv_mean must hold {C} float32 values")
+    network =bool(N.query("mw_median_is_network", sy, sx)) and not force_generic
+    with profiling.timed("median", H * W * C * (img.element_size() + out.element_size())):
+        N.call("mw_median_generic" if force_generic else "mw_median", P(img), dtype_code(img), H, W, C,
+               sy, sx, P(inv_mean), float(pseudoval), P(out), stream())
+    MEDIAN_USED["network" if network else "generic"] += 1
+    return out
+
+
 def block_mean(img: torch.Tensor, fact: int):
     H, W, C = img.shape
     Ho, Wo = -(-H // fact), -(-W // fact)
@@ -468,6 +512,8 @@ def col_stats_rows(X: torch.Tensor, stats: torch.Tensor, accumulate: bool, absma
 # deferred-blur paths taken (tests read it); *_streamed: over a slide read band by band (stream.py)
 FUSED_USED = {"sample": 0, "assign": 0, "assign_banded": 0, "sample_streamed": 0, "assign_streamed": 0,
               "nz_streamed": 0}
+# median paths taken (tests read it): the register selection network or the generic rank search
+MEDIAN_USED = {"network": 0, "generic": 0}
 
 
 def defer_blur(H: int, W: int, C: int) -> bool:
