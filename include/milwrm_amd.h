@@ -116,6 +116,26 @@ int mw_median(const void* d_img, int dtype, int H, int W, int C, int size_y, int
               const float* d_inv_mean, float pseudoval, void* d_out, void* stream);
 int mw_median_generic(const void* d_img, int dtype, int H, int W, int C, int size_y, int size_x,
                       const float* d_inv_mean, float pseudoval, void* d_out, void* stream);
+/* The row-window form (a slide streamed in row bands, milwrm_amd.stream):
+ * d_img holds the H rows [row_off, row_off + H) of a slide of slide_H rows;
+ * only the array's rows [r0, r1) are filtered, into a compact d_out of
+ * (r1 - r0) x W x C (the input's dtype, or fp32 with the lognorm epilogue).
+ * Window rows are clamped to the SLIDE, [0, slide_H - 1], not to the array;
+ * columns to [0, W - 1].  The array must hold every clamped window row of
+ * every requested output row: r0 >= size_y / 2 when row_off > 0, and H - r1 >=
+ * size_y - 1 - size_y / 2 when row_off + H < slide_H; otherwise MW_EINVAL,
+ * as for rows outside the slide or r0 >= r1 (nothing launched, d_out
+ * untouched).  Rows outside [r0, r1) are read, never computed or written, and
+ * no address outside the array is formed.  Calls over bands that tile a slide
+ * write exactly the rows of one mw_median over the whole slide, bit for bit;
+ * mw_median / mw_median_generic are the one-band case (row_off 0, slide_H =
+ * H, rows [0, H)) of the same kernel.  force_generic != 0: the rank search
+ * for every size.  Every other argument and error as mw_median. */
+int mw_median_rows(const void* d_img, int dtype, int H, int W, int C,
+                   int64_t row_off, int64_t slide_H, int r0, int r1,
+                   int size_y, int size_x, int force_generic,
+                   const float* d_inv_mean, float pseudoval,
+                   void* d_out, void* stream);
 
 /* ---- img.blurring('gaussian', sigma) (MxIF.py:375-394) ----------------------
  * Separable Gaussian, per channel, edge-replicate ('nearest'), radius r =

@@ -31,6 +31,7 @@ from .MxIF import checktype, img
 from .ST import blur_features_st
 from .dist import LOCAL_COMM
 from .rng import _release_last_draw, check_total, set_global_state_after_draws, subsample_indices_device
+from .stream import band_filter
 
 
 # ------------------------------------------------------------ k selection
@@ -156,15 +157,13 @@ def _domain_stats(image, use_path, scaler, centroids, features, tissue_ID):
     feats = image._features(features)
     mu, inv = scaler.affine()
     centroids = np.asarray(centroids, dtype=np.float64)
-    if image._pending_blur is not None:
-        # deferred blur (the fp32 blurred slide does not fit HBM): blurred band
-        # by band into a reused buffer; the exact sums make it bitwise the
-        # materialised slide's result
-        sigma, truncate = image._pending_blur
-        inv_mean, p = image._pending
-        return domain_sse_deferred(image._source() or image._device(), sigma, inv_mean, p, feats, mu,
-                                   inv, centroids, tissue_ID, truncate=truncate,
-                                   colmax=getattr(image, "_xbound", None))
+    filt = band_filter(image)
+    if filt is not None:
+        # deferred blur or median (the fp32 filtered slide does not fit HBM):
+        # filtered band by band into a reused buffer; the exact sums make it
+        # bitwise the materialised slide's result
+        return domain_sse_deferred(image._source() or image._device(), filt, feats, mu, inv, centroids,
+                                   tissue_ID, colmax=getattr(image, "_xbound", None))
     return domain_sse_image(D.as_float32(image._materialize()), feats, mu, inv, centroids, tissue_ID,
                             colmax=getattr(image, "_xbound", None))
 
@@ -283,12 +282,18 @@ def _assign_img_(image: img, features, centers, scaler, qc):
                                     truncate=truncate)
             q = None
         if res is None:
-            res = banded_assign_image(raw, sigma, inv_mean, p, feats, mu, inv, centers,
-                                      image._mask_device(), truncate=truncate, out_rows=out_rows, qc=q)
+            res = banded_assign_image(raw, band_filter(image), feats, mu, inv, centers,
+                                      image._mask_device(), out_rows=out_rows, qc=q)
         if res is None and how != "fused" and fusable:  # not even a 16-row fp32 band fits
             res = blur_assign_image(raw, sigma, inv_mean, p, mu, inv, centers, image._mask_device(),
                                     truncate=truncate)
             q = None
+        if res is not None:
+            return out(res)
+    elif image._pending_median is not None:
+        # deferred median: band by band (there is no fused median + label epilogue)
+        res = banded_assign_image(image._source() or image._device(), band_filter(image), feats, mu, inv,
+                                  centers, image._mask_device(), qc=q)
         if res is not None:
             return out(res)
     src = D.as_float32(image._materialize())
@@ -334,8 +339,12 @@ def _gather_deferred(image: img, feat, idx, r2p, X_out) -> bool:
     """Subsample rows written by the blur itself for an image whose blur is
     deferred (D.defer_blur); False when it is not, or the fused kernel does
     not take the shape (the caller materialises and gathers)."""
-    from .stream import blur_gather
+    from .stream import blur_gather, median_gather
 
+    if image._pending_median is not None:  # per band the median, then the sampled pixels copied out
+        inv_mean, p = image._pending if image._pending is not None else (None, 1.0)
+        return median_gather(image._source() or image._device(), image._pending_median, inv_mean, p, feat,
+                             idx, r2p, X_out)
     if image._pending_blur is None:
         return False
     sigma, truncate = image._pending_blur
@@ -620,13 +629,13 @@ class mxif_labeler(tissue_labeler):
         # materialised images gather by pixel: the draws become pixels through
         # the rank index first (mw_rank_to_pixel_ri), not per row in the gather
         def by_pixel(im, r2p):
-            return isinstance(r2p, D.RankIndex) and im._pending_blur is None and GATHER_BY_PIXEL
+            return isinstance(r2p, D.RankIndex) and not im._filter_deferred() and GATHER_BY_PIXEL
 
         pre = None
         # (only beside a materialised blur: a deferred slide has no blur running
         # yet, and its streamed passes want the allocator on one stream --
         # config-5 share 7.29 s in line vs 7.70 s beside)
-        if images and counts[0] and DRAWS_BESIDE and images[0]._pending_blur is None:
+        if images and counts[0] and DRAWS_BESIDE and not images[0]._filter_deferred():
             px0 = by_pixel(images[0], ranks[0][0])
             pre = _draws_beside(ranks[0][1], fract, dev, ev0, ranks[0][0] if px0 else None) + (px0,)
         # phase 2: fused lognorm+blur, gather rows into X (image_df order)

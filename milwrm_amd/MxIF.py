@@ -107,6 +107,7 @@ class img:
         self._dev = None            # HWC device tensor (authoritative when set)
         self._pending = None        # (inv_mean fp32 device tensor, pseudoval) deferred log_normalize
         self._pending_blur = None   # (sigma, truncate) deferred gaussian (fused-epilogue mode)
+        self._pending_median = None  # (size_y, size_x) deferred median (applied band by band, stream.MedianBand)
         self._lognorm_host = None   # (inv_mean fp32 host array, pseudoval) of the pending log_normalize
         self._xbound = None         # per-channel bound on |pixel| of blur(lognorm(raw)), see _blur_bound
         self.n_ch = img_arr.shape[2] if img_arr.ndim > 2 else 1
@@ -148,6 +149,15 @@ class img:
             elem = torch.empty(0, dtype=device_dtype_of(a)).element_size()
             memo = self._rawb = (a, int(a.size) * elem)
         return memo[1]
+
+    def _elem_size(self) -> int:
+        """Bytes per element of the pixels as the device holds (or would hold) them."""
+        from .stream import device_dtype_of
+
+        if self._dev is not None:
+            return self._dev.element_size()
+        t = self._src.dtype if self._host is None else device_dtype_of(self._host)
+        return torch.empty(0, dtype=t).element_size()
 
     def _device(self) -> torch.Tensor:
         """HWC device tensor (uploads on first use; a host-backed upload may
@@ -227,6 +237,7 @@ class img:
         obj._dev = None
         obj._pending = None
         obj._pending_blur = None
+        obj._pending_median = None
         obj._lognorm_host = None
         obj._xbound = None
         obj._src = src
@@ -250,8 +261,14 @@ class img:
         return obj
 
     def _materialize(self) -> torch.Tensor:
-        """Apply a deferred blur (with its log_normalize fused) or a deferred
-        log_normalize (standalone kernel)."""
+        """Apply a deferred blur (with its log_normalize fused), a deferred
+        median (the log_normalize as its epilogue) or a deferred log_normalize
+        (standalone kernel)."""
+        if self._pending_median is not None:
+            size = self._pending_median
+            inv, p = self._pending if self._pending is not None else (None, 1.0)
+            # (a slide that is not resident and does not fit: _device()'s MemoryError)
+            self._transformed(lambda: D.median(self._device(), size, inv_mean=inv, pseudoval=p))
         if self._pending_blur is not None:
             sigma, truncate = self._pending_blur
             inv, p = self._pending
@@ -273,10 +290,12 @@ class img:
         from .stream import RESIDENCY
 
         backed = self._host is not None or self._src is not None
-        state = (self._host, self._src, self._pending, self._pending_blur) if backed else None
+        state = (self._host, self._src, self._pending, self._pending_blur,
+                 self._pending_median) if backed else None
         out = make()
         self._pending = None
         self._pending_blur = None
+        self._pending_median = None
         self._set_device(out)
         if state is not None:
             self._revert = state
@@ -300,7 +319,7 @@ class img:
         transformed copy back to its deferred state."""
         rv = getattr(self, "_revert", None)
         if rv is not None:
-            self._host, self._src, self._pending, self._pending_blur = rv
+            self._host, self._src, self._pending, self._pending_blur, self._pending_median = rv
             self._revert = None
             self._host64 = None
         self._dev = None
@@ -310,7 +329,7 @@ class img:
         """The reference's float64 HWC array (materialised from HBM on read)."""
         if self._host64 is None:
             if (self._dev is None and self._host is not None and self._pending is None
-                    and self._pending_blur is None):
+                    and self._pending_blur is None and self._pending_median is None):
                 self._host64 = self._host.astype("float64")
             else:
                 t = self._materialize()
@@ -332,8 +351,14 @@ class img:
         self._hsrc = None
         self._pending = None
         self._pending_blur = None
+        self._pending_median = None
         self._lognorm_host = None
         self._xbound = None
+
+    def _filter_deferred(self) -> bool:
+        """Whether a filter (gaussian or median) is deferred: the passes that
+        need pixels recompute it band by band (milwrm_amd.stream)."""
+        return self._pending_blur is not None or self._pending_median is not None
 
     @property
     def mask(self):
@@ -419,6 +444,7 @@ class img:
         obj._dev = tensor
         obj._pending = None
         obj._pending_blur = None
+        obj._pending_median = None
         obj._lognorm_host = None
         obj._xbound = None
         obj.n_ch = int(tensor.shape[2])
@@ -565,6 +591,8 @@ class img:
             if mode != "nearest" or kwargs:
                 raise NotImplementedError(f"gaussian options {dict(mode=mode, **kwargs)} "
                                           "(only mode='nearest' is implemented)")
+            if self._pending_median is not None:  # a second filter: the deferred median applies first
+                self._materialize()
             bound = self._blur_bound()
             self._blur_(float(sigma), truncate)
             self._xbound = bound
@@ -596,7 +624,12 @@ class img:
         log_normalize alone is applied to the selected raw elements in the
         kernel's epilogue (selection commutes with the non-decreasing map:
         the same bits as normalising first); anything else pending is applied
-        first.  The whole slide must be resident (or fit: MemoryError)."""
+        first.  A slide that is not resident, or whose filtered copy may not
+        be held (the HBM budget), keeps the filter deferred
+        (``_pending_median``): every pass that needs pixels applies it band by
+        band (stream.MedianBand: the subsample, the label pass, the QC sums),
+        which gives the resident filter's bits; ``_materialize`` applies it
+        over the whole slide when that fits."""
         size = D.median_size(size)
         if getattr(self, "_band", None) is not None:
             raise NotImplementedError("median filter of a row band of a slide: the window needs the "
@@ -605,10 +638,20 @@ class img:
         bound = self._blur_bound()
         if bound is None and self._pending is None and self._pending_blur is None:
             bound = self._xbound
+        if self._pending_median is not None:  # a second filter: the deferred one applies first
+            self._materialize()
         fused = self._pending is not None and self._pending[0] is not None and self._pending_blur is None
+        if fused or self._pending is None:  # raw pixels (and a log_normalize): the state that can stay deferred
+            H, W = self.shape[0], self.shape[1]
+            if self._source() is not None or not self._may_hold(
+                    H * W * self.n_ch * (4 if fused else self._elem_size())):
+                self._pending_median = size
+                self._host64 = None
+                self._xbound = bound
+                return
         if fused:
             inv, p = self._pending
-            out = D.median(self._device(), size, inv_mean=inv, pseudoval=p)  # not resident: MemoryError
+            out = D.median(self._device(), size, inv_mean=inv, pseudoval=p)
         else:
             out = D.median(self._materialize(), size)
         self._pending = None
@@ -658,6 +701,8 @@ class img:
     def _blur_(self, sigma: float, truncate: float):
         """The gaussian branch of ``blurring``: deferred (streamed slide, or the
         fp32 copy would not fit) or materialised."""
+        if self._pending_median is not None:  # a second filter: the deferred median applies first
+            self._materialize()
         if self._pending_blur is None and self._source() is not None:
             # not resident: the blur runs inside every pass over the
             # streamed bands (stream.blur_gather, the banded label pass)
@@ -711,11 +756,11 @@ class img:
                           accumulate=False):
         """Device subsample: mask rank → legacy-RNG indices → row gather into
         ``X_out`` (fp32) with column statistics folded into ``stats``."""
-        from .stream import blur_gather
+        from .stream import blur_gather, median_gather
 
         features = self._features(features)
         np.random.seed(random_state)  # the reference's global-RNG side effect (MxIF.py:484)
-        deferred = self._pending_blur is not None
+        deferred = self._filter_deferred()
         src = None if deferred else D.as_float32(self._materialize())
         r2p, M = self._mask_rank()
         dev = D.device()
@@ -727,11 +772,15 @@ class img:
             stats = torch.zeros(1 + 2 * len(features), dtype=torch.float64, device=dev)
         if S:
             feat = D.h2d(np.asarray(features, dtype=np.int32), dev)
-            if deferred:  # rows straight from the blur (resident or streamed slide)
-                sigma, truncate = self._pending_blur
-                inv, p = self._pending
-                blur_gather(self._source() or self._device(), sigma, inv, p, feat, d_idx, r2p, X_out,
-                            truncate)
+            if deferred:  # rows straight from the filter (resident or streamed slide)
+                inv, p = self._pending if self._pending is not None else (None, 1.0)
+                if self._pending_median is not None:
+                    median_gather(self._source() or self._device(), self._pending_median, inv, p, feat,
+                                  d_idx, r2p, X_out)
+                else:
+                    sigma, truncate = self._pending_blur
+                    blur_gather(self._source() or self._device(), sigma, inv, p, feat, d_idx, r2p, X_out,
+                                truncate)
                 D.col_stats_rows(X_out, stats, accumulate)
             else:
                 D.gather_rows(src, feat, d_idx, r2p, X_out, stats, accumulate)
@@ -762,7 +811,7 @@ class img:
         integer sums for uint8 / uint16, the whole-slide bits)."""
         from . import stream
 
-        src = self._source() if self._pending is None and self._pending_blur is None else None
+        src = self._source() if self._pending is None and not self._filter_deferred() else None
         if src is not None:
             D.FUSED_USED["nz_streamed"] += 1
             return stream.nz_stats(src)

@@ -121,15 +121,17 @@ def _band_buffer(H, W, C, r, band_rows, min_band=16):
     return buf, (band_rows if got >= want else got - 2 * r)
 
 
-def banded_assign_image(raw, sigma: float, inv_mean, pseudoval: float, feat_idx, mu,
-                        inv, centers: np.ndarray, mask_u8: torch.Tensor, truncate: float = 4.0,
+def banded_assign_image(raw, filt, feat_idx, mu, inv, centers: np.ndarray, mask_u8: torch.Tensor,
                         band_rows=None, out_rows=None, qc: LabelPassQC | None = None):
-    """``assign_image(blur(lognorm(raw)))`` for a slide whose fp32 blurred copy
-    does not fit HBM: the blur is materialised one band of rows at a time
-    (band plus r halo rows of input; the kernel's arithmetic per output value
-    does not depend on the band, so labels and confidences are bitwise those
-    of the whole-slide blur) into one reused buffer, and each band goes
-    through the label pass.  The per-domain sums are added band after band.
+    """``assign_image(filtered slide)`` for a slide whose fp32 filtered copy
+    does not fit HBM.  ``filt``: the deferred filter as a band filter
+    (``stream.GaussianBand``: blur(lognorm(raw)); ``stream.MedianBand``:
+    lognorm(median(raw))).  The filter is materialised one band of rows at a
+    time (band plus ``filt.halo`` rows of input; the kernel's result per
+    output value does not depend on the band, so labels and confidences are
+    bitwise those of the whole-slide filter) into one reused buffer, and each
+    band goes through the label pass.  The per-domain sums are added band
+    after band.
     ``raw``: a resident slide or a ``stream.RowSource`` (a slide that is not
     resident: its bands are read as they are needed, the next one while this
     one is labelled).  None when not even a 16-row band fits in half the
@@ -137,14 +139,13 @@ def banded_assign_image(raw, sigma: float, inv_mean, pseudoval: float, feat_idx,
     slide band's own rows inside its halo'd array, milwrm_amd.bands); outputs
     are (r1 - r0) x W.  ``qc``: a ``LabelPassQC`` that takes every labelled
     band (whole slides only: ``out_rows`` None)."""
-    from .stream import as_source, bands
+    from .stream import as_source, filtered_bands
 
     src = as_source(raw)
     H, W, C = src.shape
     r0, r1 = (0, H) if out_rows is None else (int(out_rows[0]), int(out_rows[1]))
     k, F = centers.shape
-    w = D.gaussian_taps(sigma, truncate)
-    r = (len(w) - 1) // 2
+    r = filt.halo
     row_bytes = W * C * 4
     from .stream import RESIDENCY
 
@@ -160,15 +161,13 @@ def banded_assign_image(raw, sigma: float, inv_mean, pseudoval: float, feat_idx,
     conf = torch.empty((r1 - r0, W), dtype=torch.float32, device=dev)
     dom = torch.zeros(DOM_REC * k, dtype=torch.float64, device=dev)  # exact limbs: any band split, same bits
     buf, band_rows = _band_buffer(H, W, C, r, band_rows)
-    for y0, y1, a, rb in bands(src, band_rows, r, r0, r1):
-        out = buf[:rb.shape[0]]
-        D.blur(rb, sigma, inv_mean=inv_mean, pseudoval=pseudoval, out=out, truncate=truncate)
-        _, _, d = assign_image(out[y0 - a:y1 - a], feat_idx, mu, inv, centers,
+    for y0, y1, core in filtered_bands(src, filt, band_rows, buf, r0, r1):
+        _, _, d = assign_image(core, feat_idx, mu, inv, centers,
                                D.padded_mask(mask_u8[y0:y1].contiguous()),
                                out_lab=lab[y0 - r0:y1 - r0], out_conf=conf[y0 - r0:y1 - r0])
         dom_add_(dom, d)
         if qc is not None:  # the band is still in the buffer: its QC sums now
-            qc.band(out[y0 - a:y1 - a], lab[y0 - r0:y1 - r0])
+            qc.band(core, lab[y0 - r0:y1 - r0])
     D.FUSED_USED["assign_banded"] += 1
     if not src.zero_copy:
         D.FUSED_USED["assign_streamed"] += 1
@@ -335,27 +334,25 @@ def _first_pixel_scaled(img_f32, feat, mu, inv) -> np.ndarray:
         inv, dtype=np.float64)
 
 
-def domain_sse_deferred(raw, sigma: float, inv_mean, pseudoval: float, feat_idx, mu,
-                        inv, centers: np.ndarray, tissue_id, truncate: float = 4.0,
+def domain_sse_deferred(raw, filt, feat_idx, mu, inv, centers: np.ndarray, tissue_id,
                         band_rows=None, colmax=None) -> dict:
-    """``domain_sse_image(blur(lognorm(raw)), ...)`` for a slide whose fp32
-    blurred copy does not fit HBM (the deferred-blur mode): the blur is
-    materialised band by band (band + r halo rows of input) into one reused
+    """``domain_sse_image(filtered slide, ...)`` for a slide whose fp32
+    filtered copy does not fit HBM (the deferred mode; ``filt``: its band
+    filter, ``stream.GaussianBand`` or ``stream.MedianBand``): the filter is
+    materialised band by band (band + halo rows of input) into one reused
     buffer, twice -- once for the column maxima that fix the fixed point,
     once for the sums -- or once when ``colmax`` (a per-channel bound on |x|,
     ``img._blur_bound``) is given.  The sums are exact, so the result is
     bitwise the materialised slide's given the same bound
     (tests/test_gpu_qc.py).  ``raw``: a resident slide or a
     ``stream.RowSource`` (read band by band)."""
-    from .stream import as_source
-    from .stream import bands as read_bands
+    from .stream import as_source, filtered_bands
 
     src = as_source(raw)
     H, W, C = src.shape
     k, F = centers.shape
     feat = _check_feats(feat_idx, F, C)
-    w = D.gaussian_taps(sigma, truncate)
-    r = (len(w) - 1) // 2
+    r = filt.halo
     band_rows = _assign_band_rows(src, r, W * C * 4, band_rows)
     if band_rows < 1:
         raise MemoryError("not even one row band of the blurred slide fits in half the free HBM")
@@ -374,10 +371,7 @@ def domain_sse_deferred(raw, sigma: float, inv_mean, pseudoval: float, feat_idx,
                           f"for exact limbs and HBM holds {band_rows}")
 
     def bands():
-        for y0, y1, a, rb in read_bands(src, band_rows, r):
-            out = buf[:rb.shape[0]]
-            D.blur(rb, sigma, inv_mean=inv_mean, pseudoval=pseudoval, out=out, truncate=truncate)
-            yield y0, y1, out[y0 - a:y1 - a]
+        return filtered_bands(src, filt, band_rows, buf)
 
     acc = None
     if colmax is None:

@@ -28,6 +28,17 @@
 //     the candidate key.
 // Optional epilogue: the selected raw value goes through lognorm1 (the
 // standalone mw_lognorm's arithmetic) and is written as fp32 once.
+//
+// Row window (mw_median_rows): the array holds rows [row_off, row_off + H) of a
+// slide of slide_H rows, rows [r0, r1) of the array are filtered into a compact
+// (r1 - r0)-row output, and window rows are clamped to the SLIDE.  The entry
+// refuses an array that lacks a window row of a requested output row, so for
+// every row that is written the slide clamp and the clamp to the array pick
+// the same row: the kernel clamps to the array (no address outside it is
+// formed, also for the unwritten rows of a last partial tile) and only needs
+// r0 and r1.  A value's window holds the same elements whichever band reads
+// them, and the selection is exact: bands tile to one whole-slide call bit for
+// bit.  mw_median is the one-band case (row_off 0, slide_H = H, rows [0, H)).
 #include "common.h"
 #include "blur.h"  // lognorm1
 
@@ -42,6 +53,7 @@ constexpr int kMedThreads = 256;
 
 struct MedPlan {
   int H, W, C, sy, sx;
+  int r0, r1;   // output rows [r0, r1) of the array; the output starts at row r0
   int TW;       // output pixels per tile
   int WC;       // words per pixel in a chunk
   int KC;       // channels per chunk (pad included): WC * keys per word
@@ -155,7 +167,7 @@ __global__ void __launch_bounds__(kMedThreads) median_kernel(const T* __restrict
   const int chunk = (int)(b % (uint32_t)p.chunks);
   b /= (uint32_t)p.chunks;
   const int tx = (int)(b % (uint32_t)p.tiles_x), ty = (int)(b / (uint32_t)p.tiles_x);
-  const int x0 = tx * p.TW, y0 = ty * kMedTH, c0 = chunk * p.KC;
+  const int x0 = tx * p.TW, y0 = p.r0 + ty * kMedTH, c0 = chunk * p.KC;
   const int sy = S ? S : p.sy, sx = S ? S : p.sx;
   const int hy = sy / 2, hx = sx / 2;
   const int LW = p.TW + sx - 1, LH = kMedTH + sy - 1;
@@ -180,7 +192,7 @@ __global__ void __launch_bounds__(kMedThreads) median_kernel(const T* __restrict
     const uint32_t row = med_div(i, p.m_rw, RW), rem = i - row * RW;
     const uint32_t px = med_div(rem, p.m_wc, (uint32_t)p.WC), w = rem - px * (uint32_t)p.WC;
     const int y = y0 + (int)row, x = x0 + (int)px;
-    if (y >= p.H || x >= p.W) continue;
+    if (y >= p.r1 || x >= p.W) continue;
     const uint32_t* win = med_tile + (int)row * rstride + (int)rem;  // the window's top left word
     uint32_t res;
     if constexpr (S > 0) {
@@ -224,7 +236,7 @@ __global__ void __launch_bounds__(kMedThreads) median_kernel(const T* __restrict
         res = r0;
       }
     }
-    const int64_t o = ((int64_t)y * p.W + x) * p.C + c0 + (int)w * KPW;
+    const int64_t o = ((int64_t)(y - p.r0) * p.W + x) * p.C + c0 + (int)w * KPW;
 #pragma unroll
     for (int h = 0; h < KPW; ++h) {
       const int c = c0 + (int)w * KPW + h;
@@ -245,27 +257,27 @@ static inline uint32_t med_magic(uint32_t d) {  // ceil(2^32 / d), d >= 2 (d = 1
 static inline bool med_network(int sy, int sx) { return sy == sx && (sy == 2 || sy == 3 || sy == 5); }
 
 template <typename T, bool EPI>
-static int launch_median(const void* d_img, int H, int W, int C, int sy, int sx, bool network,
-                         const float* d_inv_mean, float pseudoval, void* d_out, hipStream_t s) {
+static int launch_median(const char* fn, const void* d_img, int H, int W, int C, int r0, int r1, int sy,
+                         int sx, bool network, const float* d_inv_mean, float pseudoval, void* d_out, hipStream_t s) {
   constexpr int KPW = 4 / (int)sizeof(typename MedKey<T>::K);
   MedPlan p;
-  p.H = H; p.W = W; p.C = C; p.sy = sy; p.sx = sx;
+  p.H = H; p.W = W; p.C = C; p.sy = sy; p.sx = sx; p.r0 = r0; p.r1 = r1;
   const int words = (C + KPW - 1) / KPW;
   p.chunks = (words + kMedMaxWC - 1) / kMedMaxWC;
   p.WC = (words + p.chunks - 1) / p.chunks;  // even chunks, at most kMedMaxWC words
   p.KC = p.WC * KPW;
   p.TW = std::min(kMedMaxTW, std::max(kMedMinTW, kMedThreads / p.WC));
   p.tiles_x = (W + p.TW - 1) / p.TW;
-  const int64_t tiles_y = ((int64_t)H + kMedTH - 1) / kMedTH;
+  const int64_t tiles_y = ((int64_t)(r1 - r0) + kMedTH - 1) / kMedTH;  // the requested rows only
   const int64_t blocks = (int64_t)p.tiles_x * tiles_y * p.chunks;
   if (blocks > 0x7fffffffll) {
-    set_error("mw_median: %lld workgroups (image too large for one launch)", (long long)blocks);
+    set_error("%s: %lld workgroups (image too large for one launch)", fn, (long long)blocks);
     return MW_EUNSUPPORTED;
   }
   const int LW = p.TW + sx - 1, LH = kMedTH + sy - 1;
   const size_t lds = (size_t)LH * LW * p.WC * 4;
   if (lds > 65536) {
-    set_error("mw_median: tile of %zu bytes does not fit in LDS", lds);
+    set_error("%s: tile of %zu bytes does not fit in LDS", fn, lds);
     return MW_EUNSUPPORTED;
   }
   p.m_kc = med_magic((uint32_t)p.KC);
@@ -285,31 +297,39 @@ static int launch_median(const void* d_img, int H, int W, int C, int sy, int sx,
   return MW_OK;
 }
 
-static int median_entry(const void* d_img, int dtype, int H, int W, int C, int sy, int sx, bool generic,
+static int median_entry(const char* fn, const void* d_img, int dtype, int H, int W, int C, int64_t row_off,
+                        int64_t slide_H, int r0, int r1, int sy, int sx, bool generic,
                         const float* d_inv_mean, float pseudoval, void* d_out, void* stream) {
-  MW_CHECK_ARG(d_img && d_out, "mw_median: null pointer");
-  MW_CHECK_ARG(H >= 1 && W >= 1 && C >= 1, "mw_median: bad shape %d x %d x %d", H, W, C);
-  MW_CHECK_ARG(sy >= 1 && sx >= 1, "mw_median: size %d x %d (each must be at least 1)", sy, sx);
-  MW_CHECK_ARG(d_out != d_img, "mw_median: the output must not alias the image");
-  MW_CHECK_ARG(dtype == MW_U8 || dtype == MW_U16 || dtype == MW_F32, "mw_median: bad dtype %d", dtype);
+  MW_CHECK_ARG(d_img && d_out, "%s: null pointer", fn);
+  MW_CHECK_ARG(H >= 1 && W >= 1 && C >= 1, "%s: bad shape %d x %d x %d", fn, H, W, C);
+  MW_CHECK_ARG(sy >= 1 && sx >= 1, "%s: size %d x %d (each must be at least 1)", fn, sy, sx);
+  MW_CHECK_ARG(d_out != d_img, "%s: the output must not alias the image", fn);
+  MW_CHECK_ARG(dtype == MW_U8 || dtype == MW_U16 || dtype == MW_F32, "%s: bad dtype %d", fn, dtype);
+  MW_CHECK_ARG(row_off >= 0 && row_off + H <= slide_H, "%s: rows [%lld, %lld) are not rows of a %lld-row slide",
+               fn, (long long)row_off, (long long)row_off + H, (long long)slide_H);
+  MW_CHECK_ARG(0 <= r0 && r0 < r1 && r1 <= H, "%s: output rows [%d, %d) of a %d-row array", fn, r0, r1, H);
   if (sy > kMedMaxSize || sx > kMedMaxSize) {
-    set_error("mw_median: size %d x %d (up to %d per axis)", sy, sx, kMedMaxSize);
+    set_error("%s: size %d x %d (up to %d per axis)", fn, sy, sx, kMedMaxSize);
     return MW_EUNSUPPORTED;
   }
+  // every window row of every requested output row, clamped to the slide, must be in the array
+  const int hy = sy / 2, below = sy - 1 - hy;
+  MW_CHECK_ARG(row_off == 0 || r0 >= hy, "%s: output row %d needs %d rows above it and the array, whose first row "
+               "is slide row %lld, holds %d", fn, r0, hy, (long long)row_off, r0);
+  MW_CHECK_ARG(row_off + H == slide_H || H - r1 >= below, "%s: output row %d needs %d rows below it and the array, "
+               "which ends before the slide does, holds %d", fn, r1 - 1, below, H - r1);
   hipStream_t s = as_stream(stream);
   const bool net = !generic && med_network(sy, sx);
   const bool epi = d_inv_mean != nullptr;
+#define MW_MED_DTYPE(T_)                                                                                         \
+  (epi ? launch_median<T_, true>(fn, d_img, H, W, C, r0, r1, sy, sx, net, d_inv_mean, pseudoval, d_out, s)       \
+       : launch_median<T_, false>(fn, d_img, H, W, C, r0, r1, sy, sx, net, d_inv_mean, pseudoval, d_out, s))
   switch (dtype) {
-    case MW_U8:
-      return epi ? launch_median<uint8_t, true>(d_img, H, W, C, sy, sx, net, d_inv_mean, pseudoval, d_out, s)
-                 : launch_median<uint8_t, false>(d_img, H, W, C, sy, sx, net, d_inv_mean, pseudoval, d_out, s);
-    case MW_U16:
-      return epi ? launch_median<uint16_t, true>(d_img, H, W, C, sy, sx, net, d_inv_mean, pseudoval, d_out, s)
-                 : launch_median<uint16_t, false>(d_img, H, W, C, sy, sx, net, d_inv_mean, pseudoval, d_out, s);
-    default:
-      return epi ? launch_median<float, true>(d_img, H, W, C, sy, sx, net, d_inv_mean, pseudoval, d_out, s)
-                 : launch_median<float, false>(d_img, H, W, C, sy, sx, net, d_inv_mean, pseudoval, d_out, s);
+    case MW_U8: return MW_MED_DTYPE(uint8_t);
+    case MW_U16: return MW_MED_DTYPE(uint16_t);
+    default: return MW_MED_DTYPE(float);
   }
+#undef MW_MED_DTYPE
 }
 
 }  // namespace mw
@@ -322,12 +342,21 @@ int mw_median_is_network(int size_y, int size_x) { return med_network(size_y, si
 
 int mw_median(const void* d_img, int dtype, int H, int W, int C, int size_y, int size_x,
               const float* d_inv_mean, float pseudoval, void* d_out, void* stream) {
-  return median_entry(d_img, dtype, H, W, C, size_y, size_x, false, d_inv_mean, pseudoval, d_out, stream);
+  return median_entry("mw_median", d_img, dtype, H, W, C, 0, H, 0, H, size_y, size_x, false, d_inv_mean,
+                      pseudoval, d_out, stream);
 }
 
 int mw_median_generic(const void* d_img, int dtype, int H, int W, int C, int size_y, int size_x,
                       const float* d_inv_mean, float pseudoval, void* d_out, void* stream) {
-  return median_entry(d_img, dtype, H, W, C, size_y, size_x, true, d_inv_mean, pseudoval, d_out, stream);
+  return median_entry("mw_median", d_img, dtype, H, W, C, 0, H, 0, H, size_y, size_x, true, d_inv_mean,
+                      pseudoval, d_out, stream);
+}
+
+int mw_median_rows(const void* d_img, int dtype, int H, int W, int C, int64_t row_off, int64_t slide_H,
+                   int r0, int r1, int size_y, int size_x, int force_generic, const float* d_inv_mean,
+                   float pseudoval, void* d_out, void* stream) {
+  return median_entry("mw_median_rows", d_img, dtype, H, W, C, row_off, slide_H, r0, r1, size_y, size_x,
+                      force_generic != 0, d_inv_mean, pseudoval, d_out, stream);
 }
 
 }  // extern "C"

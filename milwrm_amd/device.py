@@ -387,6 +387,39 @@ def median(img: torch.Tensor, size, inv_mean=None, pseudoval: float = 1.0, out=N
     return out
 
 
+def median_rows(raw: torch.Tensor, size, row_off: int, slide_H: int, r0: int, r1: int, inv_mean=None,
+                pseudoval: float = 1.0, out=None, force_generic: bool = False):
+    """``median`` over a row window (mw_median_rows): ``raw`` holds rows
+    [row_off, row_off + len(raw)) of a slide of ``slide_H`` rows, its rows
+    [r0, r1) are filtered into a compact (r1 - r0) x W x C output, and window
+    rows are clamped to the slide.  ``raw`` must hold every window row of the
+    requested rows (ValueError otherwise, nothing launched): size_y // 2 rows
+    above r0 unless it starts the slide, size_y - 1 - size_y // 2 below r1
+    unless it ends it.  Bands that tile a slide give ``median`` of the whole
+    slide bit for bit."""
+    H, W, C = raw.shape
+    sy, sx = median_size(size)
+    if not raw.is_contiguous():
+        raise ValueError("median_rows: the rows must be contiguous")
+    r0, r1 = int(r0), int(r1)
+    if not 0 <= r0 < r1 <= H:
+        raise ValueError(f"median_rows: output rows [{r0}, {r1}) of a {H}-row array")
+    out_dtype = raw.dtype if inv_mean is None else torch.float32
+    shape = (r1 - r0, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=raw.device)
+    elif out.dtype != out_dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"median_rows: out must be a contiguous {out_dtype} tensor of shape {shape}")
+    if inv_mean is not None and (inv_mean.dtype != torch.float32 or inv_mean.numel() != C):
+        raise ValueError(f"median_rows: inv_mean must hold {C} float32 values")
+    network = bool(N.query("mw_median_is_network", sy, sx)) and not force_generic
+    with profiling.timed("median", (r1 - r0) * W * C * (raw.element_size() + out.element_size())):
+        N.call("mw_median_rows", P(raw), dtype_code(raw), H, W, C, int(row_off), int(slide_H), r0, r1, sy, sx,
+               1 if force_generic else 0, P(inv_mean), float(pseudoval), P(out), stream())
+    MEDIAN_USED["network" if network else "generic"] += 1
+    return out
+
+
 def block_mean(img: torch.Tensor, fact: int):
     H, W, C = img.shape
     Ho, Wo = -(-H // fact), -(-W // fact)
@@ -509,11 +542,12 @@ def col_stats_rows(X: torch.Tensor, stats: torch.Tensor, accumulate: bool, absma
         N.call("mw_col_stats_absmax", P(ws), S, F, P(absmax), 1, stream())
 
 
-# deferred-blur paths taken (tests read it); *_streamed: over a slide read band by band (stream.py)
+# deferred-filter paths taken (blur or median; tests read it); *_streamed: over a slide read band by band (stream.py)
 FUSED_USED = {"sample": 0, "assign": 0, "assign_banded": 0, "sample_streamed": 0, "assign_streamed": 0,
               "nz_streamed": 0}
-# median paths taken (tests read it): the register selection network or the generic rank search
-MEDIAN_USED = {"network": 0, "generic": 0}
+# median paths taken (tests read it): the register selection network or the generic rank search;
+# rows_streamed: bands filtered from a slide that is not resident (stream.MedianBand)
+MEDIAN_USED = {"network": 0, "generic": 0, "rows_streamed": 0}
 
 
 def defer_blur(H: int, W: int, C: int) -> bool:

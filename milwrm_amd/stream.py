@@ -23,7 +23,12 @@ Here:
   same order whichever band holds it (the fused blur epilogues take an output
   row window: mw_blur_sample_rows / mw_blur_assign_rows; the non-zero sums of
   integer slides are exact integers), so a streamed slide gives bit for bit
-  the resident slide's results (tests/test_gpu_stream.py).
+  the resident slide's results (tests/test_gpu_stream.py);
+* a deferred filter is a band filter (``GaussianBand``, ``MedianBand``: the
+  halo it needs and the fp32 rows of a band): the subsample, the label pass
+  and the QC sums run the same loops over either.  The median is an exact
+  selection over a row window (mw_median_rows), so it streams bit for bit
+  too (tests/test_gpu_median_stream.py).
 
 Sources (``RowSource``): ``DeviceSource`` (a resident tensor; its bands are
 views, no copy), ``HostSource`` (a host array: pinned memory -- e.g.
@@ -495,24 +500,83 @@ def nz_stats(src: RowSource):
     return s, c
 
 
-def blur_gather(src, sigma: float, inv_mean, pseudoval: float, feat: torch.Tensor, idx: torch.Tensor,
-                r2p, X_out: torch.Tensor, truncate: float = 4.0, band_rows=None) -> bool:
-    """X_out[j] = blur(lognorm(slide))[pixel of rank idx[j], feat] (``r2p``: a
-    device.RankIndex or a rank -> pixel table) without storing the
-    blurred slide (``img.subsample_pixels`` after a deferred blur,
-    MxIF.py:457-492): the sample map (per pixel its first two sample slots,
-    later draws on an overflow list), then per band the blur with its sample
-    epilogue over the band's output rows (mw_blur_sample_rows) -- or, for a
-    shape the fused kernel does not take, the band blurred into fp32 and its
-    sampled pixels copied out (mw_slot_gather) -- then the overflow copies.
-    A resident slide is one band.  False when nothing was sampled."""
+class GaussianBand:
+    """The deferred Gaussian (its log_normalize fused) as the filter of a band
+    pass: ``halo`` input rows above and below a band's output rows, and
+    ``rows`` = the filtered rows as fp32."""
+
+    def __init__(self, sigma: float, inv_mean, pseudoval: float, truncate: float = 4.0):
+        self.sigma, self.inv_mean, self.pseudoval, self.truncate = sigma, inv_mean, pseudoval, truncate
+        self.taps = D.gaussian_taps(sigma, truncate)
+        self.halo = (len(self.taps) - 1) // 2
+        self.streamed = False
+
+    def rows(self, raw, a, y0, y1, H, out_f32):
+        """fp32 rows [y0, y1) of the filtered slide from ``raw`` = the slide's
+        rows from ``a`` on (the band and its halo, clipped to the ``H``-row
+        slide), through the reused band buffer ``out_f32``."""
+        out = out_f32[:raw.shape[0]]  # the blur clamps at the array's edges: exact for the core rows
+        D.blur(raw, self.sigma, inv_mean=self.inv_mean, pseudoval=self.pseudoval, out=out,
+               truncate=self.truncate)
+        return out[y0 - a:y1 - a]
+
+
+class MedianBand:
+    """The deferred median (``img._pending_median``) as a band filter: halo
+    size_y // 2; with a log_normalize pending the selected raw elements go
+    through it in the kernel's epilogue straight into the band buffer, else
+    the band is filtered in its raw type and converted (D.as_float32)."""
+
+    def __init__(self, size, inv_mean=None, pseudoval: float = 1.0):
+        self.size = D.median_size(size)
+        self.inv_mean, self.pseudoval = inv_mean, pseudoval
+        self.halo = self.size[0] // 2
+        self.streamed = False  # the bands come from a slide that is not resident (set by the pass)
+
+    def rows(self, raw, a, y0, y1, H, out_f32):
+        if self.streamed:
+            D.MEDIAN_USED["rows_streamed"] += 1
+        if self.inv_mean is not None:
+            return D.median_rows(raw, self.size, a, H, y0 - a, y1 - a, self.inv_mean, self.pseudoval,
+                                 out=out_f32[:y1 - y0])
+        return D.as_float32(D.median_rows(raw, self.size, a, H, y0 - a, y1 - a))
+
+
+def band_filter(image):
+    """The band filter of an ``img`` whose filter is deferred (Gaussian or
+    median, with the pending log_normalize as its prologue / epilogue), else
+    None."""
+    inv, p = image._pending if image._pending is not None else (None, 1.0)
+    if image._pending_blur is not None:
+        return GaussianBand(image._pending_blur[0], inv, p, image._pending_blur[1])
+    if image._pending_median is not None:
+        return MedianBand(image._pending_median, inv, p)
+    return None
+
+
+def filtered_bands(src, filt, band_rows: int, buf: torch.Tensor, r0: int = 0, r1=None):
+    """Yield (y0, y1, core): the fp32 rows [y0, y1) of ``filt`` over the slide
+    ``src``, band after band of ``bands(src, band_rows, filt.halo, r0, r1)``,
+    through the reused fp32 band buffer ``buf`` (band_rows + 2 halo rows)."""
     src = as_source(src)
+    filt.streamed = not src.zero_copy
+    for y0, y1, a, raw in bands(src, band_rows, filt.halo, r0, r1):
+        yield y0, y1, filt.rows(raw, a, y0, y1, src.H, buf)
+
+
+def _band_gather(src, filt, feat: torch.Tensor, idx: torch.Tensor, r2p, X_out: torch.Tensor, band_rows,
+                 fused=None) -> bool:
+    """X_out[j] = filtered slide[pixel of rank idx[j], feat]: the sample map
+    (per pixel its first two sample slots, later draws on an overflow list),
+    then per band ``fused(raw, a, y0, y1, slots, S)`` (a filter kernel with
+    the sample epilogue; False once: it does not take the shape) or the band
+    filtered into fp32 (``filt.rows``) and its sampled pixels copied out
+    (mw_slot_gather), then the overflow copies.  False when nothing was
+    sampled."""
     H, W, C = src.shape
     S, F = X_out.shape
     if S == 0:
         return False
-    w = D.gaussian_taps(sigma, truncate)
-    r = (len(w) - 1) // 2
     n = H * W
     slots = D.WS.get("sample_slots", 4 * N.query("mw_sample_slot_elems", n))
     ovf = D.WS.get("sample_ovf", 4 * (S + 1))
@@ -524,28 +588,19 @@ def blur_gather(src, sigma: float, inv_mean, pseudoval: float, feat: torch.Tenso
                    D.P(ovf), st)
         else:
             N.call("mw_sample_map", D.P(idx), D.P(r2p), S, n, D.P(slots), D.P(ovf), st)
-    elem = torch.empty(0, dtype=src.dtype).element_size()
-    if band_rows is None:
-        band_rows = H if src.zero_copy else band_rows_for(src)
-    fused = True
+    filt.streamed = not src.zero_copy
     fbuf = None
-    for y0, y1, a, raw in bands(src, band_rows, r):
+    for y0, y1, a, raw in bands(src, band_rows, filt.halo):
         hb = int(raw.shape[0])
-        if fused:
-            # algorithmic bytes: the band's raw rows + its share of the sampled rows written
-            with profiling.timed("blur_sample", (y1 - y0) * W * C * elem + S * F * 4 * (y1 - y0) / H):
-                fused = N.try_call("mw_blur_sample_rows", D.P(raw), D.dtype_code(raw), hb, W, C, a, y0 - a,
-                                   y1 - a, D.P(inv_mean), float(pseudoval), w.ctypes.data, r, D.P(slots), S,
-                                   D.P(feat), F, D.P(X_out), D.stream())
-            if fused:
+        if fused is not None:
+            if fused(raw, a, y0, y1, slots, S):
                 continue
-        # the fused kernel does not take this shape: blur the band into fp32
+            fused = None
+        # no fused kernel (for this shape): filter the band into fp32
         if fbuf is None:  # (bands no higher than the raw band just read)
-            fbuf = torch.empty((min(H, max(band_rows + 2 * r, hb)), W, C), dtype=torch.float32,
+            fbuf = torch.empty((min(H, max(band_rows + 2 * filt.halo, hb)), W, C), dtype=torch.float32,
                                device=raw.device)
-        out = fbuf[:hb]
-        D.blur(raw, sigma, inv_mean=inv_mean, pseudoval=pseudoval, out=out, truncate=truncate)
-        core = out[y0 - a:y1 - a]
+        core = filt.rows(raw, a, y0, y1, H, fbuf)
         with profiling.timed("slot_gather", (y1 - y0) * W * 8):
             N.call("mw_slot_gather", D.P(core), C, (y1 - y0) * W, y0 * W, D.P(slots), S, D.P(feat), F,
                    D.P(X_out), D.stream())
@@ -559,3 +614,45 @@ def blur_gather(src, sigma: float, inv_mean, pseudoval: float, feat: torch.Tenso
     if not src.zero_copy:
         D.FUSED_USED["sample_streamed"] += 1
     return True
+
+
+def blur_gather(src, sigma: float, inv_mean, pseudoval: float, feat: torch.Tensor, idx: torch.Tensor,
+                r2p, X_out: torch.Tensor, truncate: float = 4.0, band_rows=None) -> bool:
+    """X_out[j] = blur(lognorm(slide))[pixel of rank idx[j], feat] (``r2p``: a
+    device.RankIndex or a rank -> pixel table) without storing the
+    blurred slide (``img.subsample_pixels`` after a deferred blur,
+    MxIF.py:457-492): the sample map, then per band the blur with its sample
+    epilogue over the band's output rows (mw_blur_sample_rows) -- or, for a
+    shape the fused kernel does not take, the band blurred into fp32 and its
+    sampled pixels copied out -- then the overflow copies (``_band_gather``).
+    A resident slide is one band.  False when nothing was sampled."""
+    src = as_source(src)
+    H, W, C = src.shape
+    F = X_out.shape[1]
+    filt = GaussianBand(sigma, inv_mean, pseudoval, truncate)
+    w, r = filt.taps, filt.halo
+    elem = torch.empty(0, dtype=src.dtype).element_size()
+    if band_rows is None:
+        band_rows = H if src.zero_copy else band_rows_for(src)
+
+    def fused(raw, a, y0, y1, slots, S):
+        # algorithmic bytes: the band's raw rows + its share of the sampled rows written
+        with profiling.timed("blur_sample", (y1 - y0) * W * C * elem + S * F * 4 * (y1 - y0) / H):
+            return N.try_call("mw_blur_sample_rows", D.P(raw), D.dtype_code(raw), int(raw.shape[0]), W, C, a,
+                              y0 - a, y1 - a, D.P(inv_mean), float(pseudoval), w.ctypes.data, r, D.P(slots), S,
+                              D.P(feat), F, D.P(X_out), D.stream())
+
+    return _band_gather(src, filt, feat, idx, r2p, X_out, band_rows, fused)
+
+
+def median_gather(src, size, inv_mean, pseudoval: float, feat: torch.Tensor, idx: torch.Tensor, r2p,
+                  X_out: torch.Tensor, band_rows=None) -> bool:
+    """X_out[j] = lognorm(median(slide))[pixel of rank idx[j], feat] without
+    storing the filtered slide (``img.subsample_pixels`` after a deferred
+    median): per band the median over the band's output rows (mw_median_rows)
+    and the sampled pixels copied out; there is no fused sample epilogue.  A
+    resident slide is banded too: its filtered copy is what may not be held."""
+    src = as_source(src)
+    if band_rows is None:
+        band_rows = band_rows_for(src, src.W * src.C * 4)
+    return _band_gather(src, MedianBand(size, inv_mean, pseudoval), feat, idx, r2p, X_out, band_rows)
