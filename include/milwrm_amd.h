@@ -137,6 +137,39 @@ int mw_median_rows(const void* d_img, int dtype, int H, int W, int C,
                    const float* d_inv_mean, float pseudoval,
                    void* d_out, void* stream);
 
+/* ---- img.blurring('bilateral', sigma, sigma_color=v) (MxIF.py:406-410) -------
+ * Bilateral filter over all channels jointly.  a = the image as fp32: the
+ * element itself, or mw_lognorm's value of it when d_inv_mean != NULL (the
+ * log-normalise fused into the load).  For output pixel (y, x) and every tap
+ * (dy, dx) in [-radius, radius]^2, q = a[y + dy, x + dx, :]; outside the image
+ * q is cval in every channel (mode 0, 'constant') or the pixel at the clamped
+ * coordinates (mode 1, 'edge');
+ *   w = exp(-(dy^2 + dx^2) / (2 sigma_spatial^2) - |q - a[y, x, :]|^2 / (2 sigma_color^2)),
+ *   d_out[y, x, c] = sum w q[c] / sum w          (fp32; the centre tap has w = 1).
+ * This is skimage's documented denoise_bilateral without its colour look-up
+ * table, its shift of negative images and its release-specific index quirks
+ * (DESIGN.md §17).  The spatial factor comes from a table made in fp64, the
+ * colour factor and the sums are fp32.  NaN input is undefined.  The kernel
+ * filters every image; returning a constant image unchanged is the caller's
+ * rule (milwrm_amd.device.bilateral, from mw_image_moments' min and max).
+ * radius 0..12 and C <= 64 (beyond either: MW_EUNSUPPORTED, nothing launched);
+ * sigma_spatial or sigma_color not positive and finite, radius < 0, a mode
+ * other than 0 / 1, cval not finite or d_out == d_img: MW_EINVAL.  No
+ * workspace. */
+int mw_bilateral(const void* d_img, int dtype, int H, int W, int C, int radius,
+                 double sigma_spatial, double sigma_color, int mode, float cval,
+                 const float* d_inv_mean, float pseudoval, float* d_out, void* stream);
+/* d_out (device, 5 doubles): the element count n_pix * C, the mean, the
+ * centred second moment sum (a - mean)^2, the minimum and the maximum of the
+ * image a (the load transform of mw_bilateral), in fp64 by two passes (the
+ * sum, then the squared deviations) over fixed reduction trees: deterministic,
+ * and sqrt(d_out[2] / d_out[0]) is numpy's a.astype(float64).std() to about
+ * 1e-15 relative.  d_ws: mw_image_moments_ws_bytes() bytes. */
+size_t mw_image_moments_ws_bytes(void);
+int mw_image_moments(const void* d_img, int dtype, int64_t n_pix, int C,
+                     const float* d_inv_mean, float pseudoval, double* d_out,
+                     void* d_ws, void* stream);
+
 /* ---- img.blurring('gaussian', sigma) (MxIF.py:375-394) ----------------------
  * Separable Gaussian, per channel, edge-replicate ('nearest'), radius r =
  * int(4*sigma+0.5) <= 32, taps h_w[0..2r] (scipy _gaussian_kernel1d).

@@ -612,8 +612,19 @@ class img:
                 sigma = int(sigma)
             np.ones(sigma, sigma)
             raise NotImplementedError("median filter")
+        elif filter_name == "bilateral" and "sigma_color" in kwargs:
+            # only sigma_color= selects the device filter (as size= selects the
+            # median): the bare call keeps raising, below
+            sigma_color = kwargs.pop("sigma_color")
+            opts = {k: kwargs.pop(k) for k in ("win_size", "bins", "mode", "cval") if k in kwargs}
+            if kwargs:
+                raise NotImplementedError(f"bilateral options {kwargs} (sigma_color, win_size, bins, mode "
+                                          "and cval are implemented)")
+            print("Applying bilateral filter")
+            self.bilateral_filter(sigma, sigma_color, **opts)
         elif filter_name == "bilateral":
-            raise NotImplementedError("bilateral filter is outside the MI355X hot path")
+            raise NotImplementedError("bilateral filter: pass sigma_color= (a number, or 'std' for the "
+                                      "standard deviation of the whole image) to run the device filter")
         else:
             raise Exception("filter name should be either gaussian, median or bilateral")
 
@@ -656,6 +667,49 @@ class img:
             out = D.median(self._materialize(), size)
         self._pending = None
         self._pending_blur = None
+        self._set_device(out)
+        self._xbound = bound
+
+    def bilateral_filter(self, sigma, sigma_color, win_size=None, bins=None, mode="constant", cval=0):
+        """Bilateral filter over all channels jointly (D.bilateral; the
+        definition and how it differs from skimage's denoise_bilateral:
+        DESIGN.md §17).  ``sigma_color``: a positive number, or "std" for the
+        float64 standard deviation of the whole image (the reference's
+        default).  ``win_size`` defaults to max(5, 2 ceil(3 sigma) + 1), up to
+        25; ``mode`` "constant" (``cval`` outside the image) or "edge";
+        ``bins`` is accepted and ignored (the weight is exact, the limit of
+        skimage's table).  A pending log_normalize alone is fused into the
+        kernel's load (the same bits as normalising first); a pending gaussian
+        or median is applied first.  The pixels become fp32.  The slide must
+        be resident and its fp32 result must fit the HBM budget (MemoryError
+        otherwise: the banded form is not built yet)."""
+        std = isinstance(sigma_color, str) and sigma_color == "std"
+        D.bilateral_args(sigma, 1.0 if std else sigma_color, win_size, mode, cval)  # before any device call
+        if getattr(self, "_band", None) is not None:
+            raise NotImplementedError("bilateral filter of a row band of a slide: the window needs the "
+                                      "neighbour rows across the band edge")
+        # the output is a convex combination of window elements and cval
+        bound = self._blur_bound()
+        if bound is None and self._pending is None and self._pending_blur is None:
+            bound = self._xbound
+        if bound is not None:
+            bound = np.maximum(bound, abs(float(cval)))
+        if self._pending_median is not None or self._pending_blur is not None:
+            self._materialize()  # a second filter: the deferred one applies first
+        H, W = self.shape[0], self.shape[1]
+        if self._source() is not None or not self._may_hold(H * W * self.n_ch * 4):
+            raise MemoryError("bilateral filter: the slide is not resident in HBM, or its fp32 result may not "
+                              "be held under the HBM budget; the banded form of the bilateral filter is not "
+                              "built yet")
+        inv, p = self._pending if self._pending is not None else (None, 1.0)
+        src = self._device()
+        if std:
+            sigma_color = D.image_std(src, inv_mean=inv, pseudoval=p)
+            if not sigma_color > 0:  # a constant image: returned unchanged whatever the weight
+                sigma_color = 1.0
+        out = D.bilateral(src, sigma, sigma_color, win_size=win_size, mode=mode, cval=cval, inv_mean=inv,
+                          pseudoval=p)
+        self._pending = None
         self._set_device(out)
         self._xbound = bound
 

@@ -44,6 +44,10 @@ _PROTOS = {
     "mw_median_generic": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     "mw_median_rows": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
                                c_vp, c_f32, c_vp, c_vp]),
+    "mw_bilateral": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_double, C.c_double, c_i32, c_f32, c_vp,
+                             c_f32, c_vp, c_vp]),
+    "mw_image_moments_ws_bytes": (c_sz, []),
+    "mw_image_moments": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp]),
     "mw_blur_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "mw_blur": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mw_block_mean": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

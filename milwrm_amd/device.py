@@ -420,6 +420,102 @@ def median_rows(raw: torch.Tensor, size, row_off: int, slide_H: int, r0: int, r1
     return out
 
 
+BILATERAL_MAX_WIN = 25
+_BILATERAL_MODES = {"constant": 0, "edge": 1}
+
+
+def bilateral_args(sigma, sigma_color, win_size=None, mode="constant", cval=0.0):
+    """The arguments of the bilateral filter checked on the host (no device
+    call): (sigma, sigma_color, radius, mode code, cval).  ValueError: sigma or
+    sigma_color not positive and finite, win_size < 1, cval not finite;
+    NotImplementedError: win_size above 25, a mode other than 'constant' /
+    'edge'.  win_size defaults to max(5, 2 ceil(3 sigma) + 1); the radius is
+    (win_size - 1) // 2."""
+    def positive(v, name):
+        if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"bilateral {name} must be a positive finite number, got {v!r}")
+        v = float(v)
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"bilateral {name} must be a positive finite number, got {v!r}")
+        return v
+
+    sigma = positive(sigma, "sigma")
+    sigma_color = positive(sigma_color, "sigma_color")
+    if win_size is None:
+        win_size = max(5, 2 * int(np.ceil(3 * sigma)) + 1)
+    if isinstance(win_size, bool) or not isinstance(win_size, (int, np.integer)):
+        raise ValueError(f"bilateral win_size must be an int, got {win_size!r}")
+    if win_size < 1:
+        raise ValueError(f"bilateral win_size must be at least 1, got {win_size!r}")
+    if win_size > BILATERAL_MAX_WIN:
+        raise NotImplementedError(f"bilateral win_size {win_size} (up to {BILATERAL_MAX_WIN}: sigma up to 4 "
+                                  "with the default window)")
+    if mode not in _BILATERAL_MODES:
+        raise NotImplementedError(f"bilateral mode {mode!r} (only 'constant' and 'edge' are implemented)")
+    cval = float(cval)
+    if not np.isfinite(cval):
+        raise ValueError(f"bilateral cval must be finite, got {cval!r}")
+    return sigma, sigma_color, (int(win_size) - 1) // 2, _BILATERAL_MODES[mode], cval
+
+
+def _check_inv_mean(what, inv_mean, C):
+    if inv_mean is not None and (inv_mean.dtype != torch.float32 or inv_mean.numel() != C):
+        raise ValueError(f"{what}: inv_mean must hold {C} float32 values")
+
+
+def image_moments(img: torch.Tensor, inv_mean=None, pseudoval: float = 1.0) -> np.ndarray:
+    """Host float64 [n, mean, sum (a - mean)^2, min, max] of the HWC image
+    ``a`` = ``img`` as fp32, log-normalised when ``inv_mean`` is given
+    (mw_image_moments: two passes in fp64).  Synchronises on the result."""
+    H, W, C = img.shape
+    if not img.is_contiguous():
+        raise ValueError("image_moments: the image must be contiguous")
+    _check_inv_mean("image_moments", inv_mean, C)
+    out = torch.empty(5, dtype=torch.float64, device=img.device)
+    ws = WS.get("moments", N.query("mw_image_moments_ws_bytes"))
+    with profiling.timed("image_moments", 2 * H * W * C * img.element_size()):
+        N.call("mw_image_moments", P(img), dtype_code(img), H * W, C, P(inv_mean), float(pseudoval), P(out),
+               P(ws), stream())
+    return d2h(out)
+
+
+def image_std(img: torch.Tensor, inv_mean=None, pseudoval: float = 1.0) -> float:
+    """numpy's float64 population standard deviation over every element of the
+    (optionally log-normalised) fp32 image: ``a.astype(float64).std()``."""
+    m = image_moments(img, inv_mean, pseudoval)
+    return float(np.sqrt(m[2] / m[0]))
+
+
+def bilateral(img: torch.Tensor, sigma, sigma_color, win_size=None, mode="constant", cval=0.0,
+              inv_mean=None, pseudoval: float = 1.0, out=None):
+    """Bilateral filter of an HWC image over all channels jointly (mw_bilateral;
+    the definition: DESIGN.md §17), fp32 out.  ``inv_mean``: the image is raw
+    and ``lognorm`` is fused into the load: ``bilateral(lognorm(img))`` bit for
+    bit.  An image whose minimum equals its maximum comes back unchanged (as
+    fp32).  Arguments are checked on the host first (``bilateral_args``)."""
+    sigma, sigma_color, radius, mode_code, cval = bilateral_args(sigma, sigma_color, win_size, mode, cval)
+    H, W, C = img.shape
+    if not img.is_contiguous():
+        raise ValueError("bilateral: the image must be contiguous")
+    _check_inv_mean("bilateral", inv_mean, C)
+    if out is None:
+        out = torch.empty((H, W, C), dtype=torch.float32, device=img.device)
+    elif out.dtype != torch.float32 or out.shape != img.shape or not out.is_contiguous():
+        raise ValueError(f"bilateral: out must be a contiguous float32 tensor of shape {tuple(img.shape)}")
+    if out.data_ptr() == img.data_ptr():
+        raise ValueError("bilateral: the output must not alias the image")
+    m = image_moments(img, inv_mean, pseudoval)
+    if m[3] == m[4]:  # a constant image is returned as it is
+        if inv_mean is not None:
+            return lognorm(img, inv_mean, pseudoval, out=out)
+        out.copy_(as_float32(img))
+        return out
+    with profiling.timed("bilateral", H * W * C * (img.element_size() + 4)):
+        N.call("mw_bilateral", P(img), dtype_code(img), H, W, C, radius, sigma, sigma_color, mode_code, cval,
+               P(inv_mean), float(pseudoval), P(out), stream())
+    return out
+
+
 def block_mean(img: torch.Tensor, fact: int):
     H, W, C = img.shape
     Ho, Wo = -(-H // fact), -(-W // fact)
