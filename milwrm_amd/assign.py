@@ -36,6 +36,8 @@ def assign_image(img_f32: torch.Tensor, feat_idx, mu, inv, centers: np.ndarray,
     dom = torch.empty(DOM_REC * k, dtype=torch.float64, device=dev)
     ws = D.WS.get("assign", N.query("mw_assign_ws_bytes", n, k))
     st = D.stream()
+    # credited bytes: every pixel's features, although the kernel does not read
+    # 64-pixel tiles that lie wholly outside the mask
     with profiling.timed("assign_conf", n * (C * 4 + 1 + 5)):
         N.call("mw_assign_conf", D.P(img_f32), C, D.P(feat), F, D.P(a), D.P(b), D.P(c32), k,
                D.P(mask_u8), n, D.P(lab), D.P(conf), D.P(ws), st)

@@ -225,10 +225,23 @@ __global__ void __launch_bounds__(256, kAssignWPS) assign_kernel(const float* __
   // two tiles in flight per wave (register ring): the LDS footprint allows
   // 2 waves per SIMD, and one 7.7-KB tile per wave in flight left the pass
   // latency-bound (~4.2 TB/s)
-  auto fetch = [&](f4v (&vv)[NV], int& mm, int tt) {
+  // A tile with no pixel inside the mask is not read: its outputs are -1 /
+  // NaN whatever its features hold, and its pixels would only add to the
+  // sink slot k, which no record reads.  The mask byte runs one tile ahead of
+  // the planes (mn: requested by the slot's previous fetch, ahead of that
+  // fetch's plane loads), so the ballot never waits on a load of its own fetch
+  constexpr int kSlots = XL ? 1 : 2;  // XL: one tile in flight per wave (more waves)
+  auto mask_byte = [&](int tt) -> int {
+    tt = tt < ntile ? tt : ntile - 1;
+    return ld_stream(mask + min(lo + (int64_t)tt * 64 + lane, hi - 1));  // nt: read-once streams
+  };
+  auto fetch = [&](f4v (&vv)[NV], int& mm, int& mn, bool& sk, int tt) {
     tt = tt < ntile ? tt : ntile - 1;
     const int64_t r = lo + (int64_t)tt * 64;
-    mm = ld_stream(mask + min(r + lane, hi - 1));  // nt: read-once streams
+    mm = mn;
+    mn = mask_byte(tt + kSlots * tstep);
+    sk = __ballot(r + lane < hi && mm != 0) == 0;  // wave-uniform
+    if (sk) return;  // vv stays stale: body() does not read it
     const int64_t q0 = (r * C) >> 2;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -237,18 +250,30 @@ __global__ void __launch_bounds__(256, kAssignWPS) assign_kernel(const float* __
       vv[i] = ld_stream(X4 + q);
     }
   };
-  auto body = [&](f4v (&vv)[NV], int& mm, int tc) {
+  auto body = [&](f4v (&vv)[NV], int& mm, int& mn, bool& sk, int tc) {
     const int64_t p0 = lo + (int64_t)tc * 64;
     const int np = (int)min((int64_t)64, hi - p0);
-    {
+    const bool skip = sk;
+    if (!skip) {
       f4v* s4 = reinterpret_cast<f4v*>(s_tile);
 #pragma unroll
       for (int i = 0; i < NV; ++i)  // XL: the slot holds 64 * C floats (+ pad), not 64 * CMAX
         if (!XL || (lane + i * 64) * 4 < 64 * C) s4[lane + i * 64] = vv[i];
+      wt_tail(np * C, p0 * C, n4, img, total, s_tile, lane);
+      // the last row's pairs past C read the next tile's first floats (times
+      // the padded scaler 0): zero, as in the XL slot, so that a tile which
+      // may be skipped is not looked at from here either (NaN * 0 is not 0)
+      if (!XL && lane < CMAX - C) s_tile[64 * C + lane] = 0.f;
     }
-    wt_tail(np * C, p0 * C, n4, img, total, s_tile, lane);
     const int mk = mm;
-    fetch(vv, mm, tc + (XL ? 1 : 2) * tstep);  // XL: one tile in flight per wave (more waves)
+    fetch(vv, mm, mn, sk, tc + kSlots * tstep);
+    if (skip) {
+      if (lane < np) {
+        lab_out[p0 + lane] = (int8_t)-1;
+        conf_out[p0 + lane] = __builtin_nanf("");
+      }
+      return;
+    }
     float m1, m2;
     int lab;
     if constexpr (XL) {  // the scaled row stays in LDS (SC centers): CMAX VGPRs fewer
@@ -305,19 +330,26 @@ __global__ void __launch_bounds__(256, kAssignWPS) assign_kernel(const float* __
   int tc = tc0;
   if constexpr (XL) {
     f4v va[NV];
-    int ma = 0;
-    if (tc < ntile) fetch(va, ma, tc);
-    for (; tc < ntile; tc += tstep) body(va, ma, tc);
+    int ma = 0, na = 0;
+    bool ka = true;
+    if (tc < ntile) {
+      na = mask_byte(tc);  // the one mask byte a wave waits for by itself
+      fetch(va, ma, na, ka, tc);
+    }
+    for (; tc < ntile; tc += tstep) body(va, ma, na, ka, tc);
   } else {
     f4v va[NV], vb[NV];
-    int ma = 0, mb = 0;
+    int ma = 0, mb = 0, na = 0, nb = 0;
+    bool ka = true, kb = true;
     if (tc < ntile) {
-      fetch(va, ma, tc);
-      fetch(vb, mb, tc + tstep);
+      na = mask_byte(tc);
+      nb = mask_byte(tc + tstep);
+      fetch(va, ma, na, ka, tc);
+      fetch(vb, mb, nb, kb, tc + tstep);
     }
     for (; tc < ntile; tc += 2 * tstep) {
-      body(va, ma, tc);
-      if (tc + tstep < ntile) body(vb, mb, tc + tstep);
+      body(va, ma, na, ka, tc);
+      if (tc + tstep < ntile) body(vb, mb, nb, kb, tc + tstep);
     }
   }
   if constexpr (XL) {  // lane-private slots, as the LDS-sum form leaves them
