@@ -159,6 +159,26 @@ int mw_median_rows(const void* d_img, int dtype, int H, int W, int C,
 int mw_bilateral(const void* d_img, int dtype, int H, int W, int C, int radius,
                  double sigma_spatial, double sigma_color, int mode, float cval,
                  const float* d_inv_mean, float pseudoval, float* d_out, void* stream);
+/* The row-window form (a slide streamed in row bands, milwrm_amd.stream):
+ * d_img holds the H rows [row_off, row_off + H) of a slide of slide_H rows;
+ * only the array's rows [r0, r1) are filtered, into a compact fp32 d_out of
+ * (r1 - r0) x W x C.  A tap row is inside or outside relative to the SLIDE:
+ * mode 0 takes cval for a tap row outside [0, slide_H), mode 1 clamps tap rows
+ * to [0, slide_H - 1]; columns as mw_bilateral.  The array must hold every
+ * in-slide tap row of every requested output row: r0 >= radius when row_off >
+ * 0, and H - r1 >= radius when row_off + H < slide_H; otherwise MW_EINVAL, as
+ * for rows outside the slide or r0 >= r1 (nothing launched, d_out untouched).
+ * Rows outside [r0, r1) are read, never computed or written, and no address
+ * outside the array is formed.  A pixel's taps are summed in one order
+ * whichever tile or band computes it: calls over bands that tile a slide
+ * write exactly the rows of one mw_bilateral over the whole slide, bit for
+ * bit; mw_bilateral is the one-band case (row_off 0, slide_H = H, rows
+ * [0, H)) of the same kernel.  Every other argument and error as
+ * mw_bilateral. */
+int mw_bilateral_rows(const void* d_img, int dtype, int H, int W, int C,
+                      int64_t row_off, int64_t slide_H, int r0, int r1, int radius,
+                      double sigma_spatial, double sigma_color, int mode, float cval,
+                      const float* d_inv_mean, float pseudoval, float* d_out, void* stream);
 /* d_out (device, 5 doubles): the element count n_pix * C, the mean, the
  * centred second moment sum (a - mean)^2, the minimum and the maximum of the
  * image a (the load transform of mw_bilateral), in fp64 by two passes (the
@@ -169,6 +189,25 @@ size_t mw_image_moments_ws_bytes(void);
 int mw_image_moments(const void* d_img, int dtype, int64_t n_pix, int C,
                      const float* d_inv_mean, float pseudoval, double* d_out,
                      void* d_ws, void* stream);
+/* The same five numbers of a slide that arrives in row bands, with bits that
+ * do not depend on the bands (they differ from mw_image_moments' in the
+ * summation order only).  d_ws: mw_image_moments_rows_ws_bytes(slide_H)
+ * bytes, a table with one entry per slide row, kept by the caller from the
+ * first call to the last.  mw_image_moments_rows reduces each of the H rows
+ * [row_off, row_off + H) held by d_img with one workgroup into its entry:
+ * pass 0 the row's sum, minimum and maximum; pass 1 its sum (a - mean)^2, mean
+ * as the last mw_image_moments_rows_final left it.  Once every slide row has
+ * been through a pass, mw_image_moments_rows_final reduces the table by a
+ * fixed tree into d_out and keeps the mean in d_ws: with_m2 == 0 after pass 0
+ * (d_out[2] is NaN), != 0 after pass 1.  So: pass 0 over all bands, final(0),
+ * and for the second moment pass 1 over all bands, final(1).  Rows that are
+ * not rows of the slide, a pass other than 0 / 1: MW_EINVAL. */
+size_t mw_image_moments_rows_ws_bytes(int64_t slide_H);
+int mw_image_moments_rows(const void* d_img, int dtype, int H, int W, int C,
+                          int64_t row_off, int64_t slide_H, int pass,
+                          const float* d_inv_mean, float pseudoval, void* d_ws, void* stream);
+int mw_image_moments_rows_final(int64_t slide_H, int W, int C, int with_m2,
+                                void* d_ws, double* d_out, void* stream);
 
 /* ---- img.blurring('gaussian', sigma) (MxIF.py:375-394) ----------------------
  * Separable Gaussian, per channel, edge-replicate ('nearest'), radius r =

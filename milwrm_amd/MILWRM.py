@@ -159,7 +159,7 @@ def _domain_stats(image, use_path, scaler, centroids, features, tissue_ID):
     centroids = np.asarray(centroids, dtype=np.float64)
     filt = band_filter(image)
     if filt is not None:
-        # deferred blur or median (the fp32 filtered slide does not fit HBM):
+        # deferred blur, median or bilateral (the fp32 filtered slide does not fit HBM):
         # filtered band by band into a reused buffer; the exact sums make it
         # bitwise the materialised slide's result
         return domain_sse_deferred(image._source() or image._device(), filt, feats, mu, inv, centroids,
@@ -290,8 +290,8 @@ def _assign_img_(image: img, features, centers, scaler, qc):
             q = None
         if res is not None:
             return out(res)
-    elif image._pending_median is not None:
-        # deferred median: band by band (there is no fused median + label epilogue)
+    elif image._pending_median is not None or image._pending_bilateral is not None:
+        # deferred median or bilateral: band by band (neither has a fused label epilogue)
         res = banded_assign_image(image._source() or image._device(), band_filter(image), feats, mu, inv,
                                   centers, image._mask_device(), qc=q)
         if res is not None:
@@ -339,12 +339,16 @@ def _gather_deferred(image: img, feat, idx, r2p, X_out) -> bool:
     """Subsample rows written by the blur itself for an image whose blur is
     deferred (D.defer_blur); False when it is not, or the fused kernel does
     not take the shape (the caller materialises and gathers)."""
-    from .stream import blur_gather, median_gather
+    from .stream import bilateral_gather, blur_gather, median_gather
 
     if image._pending_median is not None:  # per band the median, then the sampled pixels copied out
         inv_mean, p = image._pending if image._pending is not None else (None, 1.0)
         return median_gather(image._source() or image._device(), image._pending_median, inv_mean, p, feat,
                              idx, r2p, X_out)
+    if image._pending_bilateral is not None:  # the same, with the bilateral
+        inv_mean, p = image._pending if image._pending is not None else (None, 1.0)
+        return bilateral_gather(image._source() or image._device(), image._pending_bilateral, inv_mean, p, feat,
+                                idx, r2p, X_out)
     if image._pending_blur is None:
         return False
     sigma, truncate = image._pending_blur
@@ -560,7 +564,9 @@ class mxif_labeler(tissue_labeler):
         StandardScaler from device column statistics.  With a sharded
         ``comm`` (milwrm_amd.dist) each rank holds its own slides and the
         statistics are merged across ranks.  ``filter_kwargs``: further
-        keywords of ``img.blurring`` (``{"size": k}`` for the median filter)."""
+        keywords of ``img.blurring`` (``{"size": k}`` for the median filter,
+        ``{"sigma_color": v}`` for the bilateral, with ``"banded": True`` to
+        let it run on slides that are streamed in row bands)."""
         comm = LOCAL_COMM if comm is None else comm
         self._comm = comm
         self._mbl = None

@@ -108,6 +108,8 @@ class img:
         self._pending = None        # (inv_mean fp32 device tensor, pseudoval) deferred log_normalize
         self._pending_blur = None   # (sigma, truncate) deferred gaussian (fused-epilogue mode)
         self._pending_median = None  # (size_y, size_x) deferred median (applied band by band, stream.MedianBand)
+        # (sigma, sigma_color as a resolved float, win_size, mode, cval) deferred bilateral (stream.BilateralBand)
+        self._pending_bilateral = None
         self._lognorm_host = None   # (inv_mean fp32 host array, pseudoval) of the pending log_normalize
         self._xbound = None         # per-channel bound on |pixel| of blur(lognorm(raw)), see _blur_bound
         self.n_ch = img_arr.shape[2] if img_arr.ndim > 2 else 1
@@ -238,6 +240,7 @@ class img:
         obj._pending = None
         obj._pending_blur = None
         obj._pending_median = None
+        obj._pending_bilateral = None
         obj._lognorm_host = None
         obj._xbound = None
         obj._src = src
@@ -262,8 +265,21 @@ class img:
 
     def _materialize(self) -> torch.Tensor:
         """Apply a deferred blur (with its log_normalize fused), a deferred
-        median (the log_normalize as its epilogue) or a deferred log_normalize
-        (standalone kernel)."""
+        median (the log_normalize as its epilogue), a deferred bilateral (the
+        log_normalize as its load) or a deferred log_normalize (standalone
+        kernel)."""
+        if self._pending_bilateral is not None:
+            sigma, sigma_color, win_size, mode, cval = self._pending_bilateral
+            inv, p = self._pending if self._pending is not None else (None, 1.0)
+
+            def make():
+                # (a slide that is not resident and does not fit: _device()'s MemoryError)
+                src = self._device()
+                # the one-band case of the bands' kernel; the constant-image rule was settled at call time
+                return D.bilateral_rows(src, sigma, sigma_color, 0, src.shape[0], 0, src.shape[0],
+                                        win_size=win_size, mode=mode, cval=cval, inv_mean=inv, pseudoval=p)
+
+            self._transformed(make)
         if self._pending_median is not None:
             size = self._pending_median
             inv, p = self._pending if self._pending is not None else (None, 1.0)
@@ -291,11 +307,12 @@ class img:
 
         backed = self._host is not None or self._src is not None
         state = (self._host, self._src, self._pending, self._pending_blur,
-                 self._pending_median) if backed else None
+                 self._pending_median, self._pending_bilateral) if backed else None
         out = make()
         self._pending = None
         self._pending_blur = None
         self._pending_median = None
+        self._pending_bilateral = None
         self._set_device(out)
         if state is not None:
             self._revert = state
@@ -319,7 +336,8 @@ class img:
         transformed copy back to its deferred state."""
         rv = getattr(self, "_revert", None)
         if rv is not None:
-            self._host, self._src, self._pending, self._pending_blur, self._pending_median = rv
+            (self._host, self._src, self._pending, self._pending_blur, self._pending_median,
+             self._pending_bilateral) = rv
             self._revert = None
             self._host64 = None
         self._dev = None
@@ -329,7 +347,8 @@ class img:
         """The reference's float64 HWC array (materialised from HBM on read)."""
         if self._host64 is None:
             if (self._dev is None and self._host is not None and self._pending is None
-                    and self._pending_blur is None and self._pending_median is None):
+                    and self._pending_blur is None and self._pending_median is None
+                    and self._pending_bilateral is None):
                 self._host64 = self._host.astype("float64")
             else:
                 t = self._materialize()
@@ -352,13 +371,15 @@ class img:
         self._pending = None
         self._pending_blur = None
         self._pending_median = None
+        self._pending_bilateral = None
         self._lognorm_host = None
         self._xbound = None
 
     def _filter_deferred(self) -> bool:
-        """Whether a filter (gaussian or median) is deferred: the passes that
-        need pixels recompute it band by band (milwrm_amd.stream)."""
-        return self._pending_blur is not None or self._pending_median is not None
+        """Whether a filter (gaussian, median or bilateral) is deferred: the
+        passes that need pixels recompute it band by band (milwrm_amd.stream)."""
+        return (self._pending_blur is not None or self._pending_median is not None
+                or self._pending_bilateral is not None)
 
     @property
     def mask(self):
@@ -445,6 +466,7 @@ class img:
         obj._pending = None
         obj._pending_blur = None
         obj._pending_median = None
+        obj._pending_bilateral = None
         obj._lognorm_host = None
         obj._xbound = None
         obj.n_ch = int(tensor.shape[2])
@@ -591,8 +613,8 @@ class img:
             if mode != "nearest" or kwargs:
                 raise NotImplementedError(f"gaussian options {dict(mode=mode, **kwargs)} "
                                           "(only mode='nearest' is implemented)")
-            if self._pending_median is not None:  # a second filter: the deferred median applies first
-                self._materialize()
+            if self._pending_median is not None or self._pending_bilateral is not None:
+                self._materialize()  # a second filter: the deferred one applies first
             bound = self._blur_bound()
             self._blur_(float(sigma), truncate)
             self._xbound = bound
@@ -616,10 +638,10 @@ class img:
             # only sigma_color= selects the device filter (as size= selects the
             # median): the bare call keeps raising, below
             sigma_color = kwargs.pop("sigma_color")
-            opts = {k: kwargs.pop(k) for k in ("win_size", "bins", "mode", "cval") if k in kwargs}
+            opts = {k: kwargs.pop(k) for k in ("win_size", "bins", "mode", "cval", "banded") if k in kwargs}
             if kwargs:
-                raise NotImplementedError(f"bilateral options {kwargs} (sigma_color, win_size, bins, mode "
-                                          "and cval are implemented)")
+                raise NotImplementedError(f"bilateral options {kwargs} (sigma_color, win_size, bins, mode, "
+                                          "cval and banded are implemented)")
             print("Applying bilateral filter")
             self.bilateral_filter(sigma, sigma_color, **opts)
         elif filter_name == "bilateral":
@@ -649,8 +671,8 @@ class img:
         bound = self._blur_bound()
         if bound is None and self._pending is None and self._pending_blur is None:
             bound = self._xbound
-        if self._pending_median is not None:  # a second filter: the deferred one applies first
-            self._materialize()
+        if self._pending_median is not None or self._pending_bilateral is not None:
+            self._materialize()  # a second filter: the deferred one applies first
         fused = self._pending is not None and self._pending[0] is not None and self._pending_blur is None
         if fused or self._pending is None:  # raw pixels (and a log_normalize): the state that can stay deferred
             H, W = self.shape[0], self.shape[1]
@@ -670,7 +692,8 @@ class img:
         self._set_device(out)
         self._xbound = bound
 
-    def bilateral_filter(self, sigma, sigma_color, win_size=None, bins=None, mode="constant", cval=0):
+    def bilateral_filter(self, sigma, sigma_color, win_size=None, bins=None, mode="constant", cval=0,
+                         banded=False):
         """Bilateral filter over all channels jointly (D.bilateral; the
         definition and how it differs from skimage's denoise_bilateral:
         DESIGN.md §17).  ``sigma_color``: a positive number, or "std" for the
@@ -680,9 +703,21 @@ class img:
         ``bins`` is accepted and ignored (the weight is exact, the limit of
         skimage's table).  A pending log_normalize alone is fused into the
         kernel's load (the same bits as normalising first); a pending gaussian
-        or median is applied first.  The pixels become fp32.  The slide must
-        be resident and its fp32 result must fit the HBM budget (MemoryError
-        otherwise: the banded form is not built yet)."""
+        or median is applied first.  The pixels become fp32.
+
+        ``banded=False``: the slide must be resident and its fp32 result must
+        fit the HBM budget (MemoryError otherwise).  ``banded=True`` permits
+        the banded form: a slide that is not resident, or whose
+        fp32 result may not be held, keeps the filter deferred
+        (``_pending_bilateral``) and every pass that needs pixels -- the
+        subsample, the label pass and the QC sums, each of them -- recomputes
+        it band by band (stream.BilateralBand), with the resident filter's
+        bits.  The bilateral is the heaviest stage per pixel, so a deferred one
+        costs about three whole-slide filters per fit instead of one, plus one
+        or two reads of the slide at the call for the whole-slide minimum,
+        maximum and ("std") standard deviation (stream.image_moments): the
+        caller chooses that knowingly.  A resident slide whose result may be
+        held is filtered at once, exactly as with ``banded=False``."""
         std = isinstance(sigma_color, str) and sigma_color == "std"
         D.bilateral_args(sigma, 1.0 if std else sigma_color, win_size, mode, cval)  # before any device call
         if getattr(self, "_band", None) is not None:
@@ -694,13 +729,18 @@ class img:
             bound = self._xbound
         if bound is not None:
             bound = np.maximum(bound, abs(float(cval)))
-        if self._pending_median is not None or self._pending_blur is not None:
+        if self._filter_deferred():
             self._materialize()  # a second filter: the deferred one applies first
         H, W = self.shape[0], self.shape[1]
-        if self._source() is not None or not self._may_hold(H * W * self.n_ch * 4):
-            raise MemoryError("bilateral filter: the slide is not resident in HBM, or its fp32 result may not "
-                              "be held under the HBM budget; the banded form of the bilateral filter is not "
-                              "built yet")
+        rsrc = self._source()
+        if rsrc is not None or not self._may_hold(H * W * self.n_ch * 4):
+            if not banded:
+                raise MemoryError("bilateral filter: the slide is not resident in HBM, or its fp32 result may "
+                                  "not be held under the HBM budget; pass banded=True for the banded form of "
+                                  "the bilateral filter (every pass that needs pixels then recomputes it band "
+                                  "by band)")
+            self._bilateral_deferred(rsrc, sigma, sigma_color, std, win_size, mode, cval, bound)
+            return
         inv, p = self._pending if self._pending is not None else (None, 1.0)
         src = self._device()
         if std:
@@ -713,10 +753,30 @@ class img:
         self._set_device(out)
         self._xbound = bound
 
+    def _bilateral_deferred(self, rsrc, sigma, sigma_color, std, win_size, mode, cval, bound):
+        """The banded form of ``bilateral_filter``: the whole-slide moments now
+        (over the source, or over the resident raw slide as a source: the same
+        bits either way), then the filter stays deferred.  A constant slide is
+        left as it is -- the filter is the identity by definition -- with a
+        pending log_normalize still pending."""
+        from . import stream
+
+        inv, p = self._pending if self._pending is not None else (None, 1.0)
+        m = stream.image_moments(rsrc if rsrc is not None else self._device(), inv, p, m2=std)
+        if m[3] == m[4]:
+            return
+        if std:
+            sigma_color = float(np.sqrt(m[2] / m[0]))
+            if not sigma_color > 0:
+                sigma_color = 1.0
+        self._pending_bilateral = (float(sigma), float(sigma_color), win_size, mode, float(cval))
+        self._host64 = None
+        self._xbound = bound
+
     def _raw_int_max(self):
         """The largest value the current pixels' element type holds when they
         are a raw uint8 / uint16 slide (device, host or streamed), else None."""
-        if self._pending_blur is not None:
+        if self._pending_blur is not None or self._pending_bilateral is not None:
             return None
         if self._dev is not None:
             t = self._dev.dtype
@@ -755,8 +815,8 @@ class img:
     def _blur_(self, sigma: float, truncate: float):
         """The gaussian branch of ``blurring``: deferred (streamed slide, or the
         fp32 copy would not fit) or materialised."""
-        if self._pending_median is not None:  # a second filter: the deferred median applies first
-            self._materialize()
+        if self._pending_median is not None or self._pending_bilateral is not None:
+            self._materialize()  # a second filter: the deferred one applies first
         if self._pending_blur is None and self._source() is not None:
             # not resident: the blur runs inside every pass over the
             # streamed bands (stream.blur_gather, the banded label pass)
@@ -794,8 +854,10 @@ class img:
             s, _ = self._nz_stats()  # zeros add nothing: channel sum over all pixels
             n = self.shape[0] * self.shape[1]
             mean = s.cpu().numpy() / n
-        elif self._pending is not None or self._pending_blur is not None:
-            self._materialize()  # a transform already pending applies first
+        elif self._pending is not None or self._pending_blur is not None or self._pending_bilateral is not None:
+            # a transform already pending applies first (the median commutes with the
+            # log and stays deferred; the bilateral does not)
+            self._materialize()
         mean = np.asarray(mean, dtype=np.float64)
         with np.errstate(divide="ignore"):
             inv = (1.0 / mean).astype(np.float32)
@@ -810,7 +872,7 @@ class img:
                           accumulate=False):
         """Device subsample: mask rank → legacy-RNG indices → row gather into
         ``X_out`` (fp32) with column statistics folded into ``stats``."""
-        from .stream import blur_gather, median_gather
+        from .stream import bilateral_gather, blur_gather, median_gather
 
         features = self._features(features)
         np.random.seed(random_state)  # the reference's global-RNG side effect (MxIF.py:484)
@@ -831,6 +893,9 @@ class img:
                 if self._pending_median is not None:
                     median_gather(self._source() or self._device(), self._pending_median, inv, p, feat,
                                   d_idx, r2p, X_out)
+                elif self._pending_bilateral is not None:
+                    bilateral_gather(self._source() or self._device(), self._pending_bilateral, inv, p, feat,
+                                     d_idx, r2p, X_out)
                 else:
                     sigma, truncate = self._pending_blur
                     blur_gather(self._source() or self._device(), sigma, inv, p, feat, d_idx, r2p, X_out,

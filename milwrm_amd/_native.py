@@ -46,6 +46,12 @@ _PROTOS = {
                                c_vp, c_f32, c_vp, c_vp]),
     "mw_bilateral": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_double, C.c_double, c_i32, c_f32, c_vp,
                              c_f32, c_vp, c_vp]),
+    "mw_bilateral_rows": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, C.c_double,
+                                  C.c_double, c_i32, c_f32, c_vp, c_f32, c_vp, c_vp]),
+    "mw_image_moments_rows_ws_bytes": (c_sz, [c_i64]),
+    "mw_image_moments_rows": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_vp, c_f32, c_vp,
+                                      c_vp]),
+    "mw_image_moments_rows_final": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mw_image_moments_ws_bytes": (c_sz, []),
     "mw_image_moments": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp]),
     "mw_blur_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),

@@ -128,7 +128,8 @@ def banded_assign_image(raw, filt, feat_idx, mu, inv, centers: np.ndarray, mask_
     """``assign_image(filtered slide)`` for a slide whose fp32 filtered copy
     does not fit HBM.  ``filt``: the deferred filter as a band filter
     (``stream.GaussianBand``: blur(lognorm(raw)); ``stream.MedianBand``:
-    lognorm(median(raw))).  The filter is materialised one band of rows at a
+    lognorm(median(raw)); ``stream.BilateralBand``: bilateral(lognorm(raw))).
+    The filter is materialised one band of rows at a
     time (band plus ``filt.halo`` rows of input; the kernel's result per
     output value does not depend on the band, so labels and confidences are
     bitwise those of the whole-slide filter) into one reused buffer, and each
@@ -340,7 +341,8 @@ def domain_sse_deferred(raw, filt, feat_idx, mu, inv, centers: np.ndarray, tissu
                         band_rows=None, colmax=None) -> dict:
     """``domain_sse_image(filtered slide, ...)`` for a slide whose fp32
     filtered copy does not fit HBM (the deferred mode; ``filt``: its band
-    filter, ``stream.GaussianBand`` or ``stream.MedianBand``): the filter is
+    filter, ``stream.GaussianBand``, ``stream.MedianBand`` or
+    ``stream.BilateralBand``): the filter is
     materialised band by band (band + halo rows of input) into one reused
     buffer, twice -- once for the column maxima that fix the fixed point,
     once for the sums -- or once when ``colmax`` (a per-channel bound on |x|,

@@ -516,6 +516,47 @@ def bilateral(img: torch.Tensor, sigma, sigma_color, win_size=None, mode="consta
     return out
 
 
+def bilateral_rows(raw: torch.Tensor, sigma, sigma_color, row_off: int, slide_H: int, r0: int, r1: int,
+                   win_size=None, mode="constant", cval=0.0, inv_mean=None, pseudoval: float = 1.0, out=None):
+    """``bilateral`` over a row window (mw_bilateral_rows): ``raw`` holds rows
+    [row_off, row_off + len(raw)) of a slide of ``slide_H`` rows, its rows
+    [r0, r1) are filtered into a compact (r1 - r0) x W x C fp32 output, and a
+    tap row is inside or outside relative to the slide.  ``raw`` must hold
+    every in-slide tap row of the requested rows (ValueError otherwise,
+    nothing launched): radius rows above r0 unless it starts the slide, radius
+    rows below r1 unless it ends it.  Bands that tile a slide give the rows of
+    mw_bilateral over the whole slide bit for bit.  The constant-image rule of
+    ``bilateral`` is NOT applied: a band cannot know the slide's minimum and
+    maximum, the caller owns that rule (``stream.image_moments``)."""
+    sigma, sigma_color, radius, mode_code, cval = bilateral_args(sigma, sigma_color, win_size, mode, cval)
+    H, W, C = raw.shape
+    if not raw.is_contiguous():
+        raise ValueError("bilateral_rows: the rows must be contiguous")
+    _check_inv_mean("bilateral_rows", inv_mean, C)
+    row_off, slide_H, r0, r1 = int(row_off), int(slide_H), int(r0), int(r1)
+    if not (0 <= row_off and row_off + H <= slide_H):
+        raise ValueError(f"bilateral_rows: rows [{row_off}, {row_off + H}) are not rows of a {slide_H}-row slide")
+    if not 0 <= r0 < r1 <= H:
+        raise ValueError(f"bilateral_rows: output rows [{r0}, {r1}) of a {H}-row array")
+    if row_off > 0 and r0 < radius:
+        raise ValueError(f"bilateral_rows: output row {r0} needs {radius} rows above it and the array, whose "
+                         f"first row is slide row {row_off}, holds {r0}")
+    if row_off + H < slide_H and H - r1 < radius:
+        raise ValueError(f"bilateral_rows: output row {r1 - 1} needs {radius} rows below it and the array, "
+                         f"which ends before the slide does, holds {H - r1}")
+    shape = (r1 - r0, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=raw.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"bilateral_rows: out must be a contiguous float32 tensor of shape {shape}")
+    if out.data_ptr() == raw.data_ptr():
+        raise ValueError("bilateral_rows: the output must not alias the rows")
+    with profiling.timed("bilateral", (r1 - r0) * W * C * (raw.element_size() + 4)):
+        N.call("mw_bilateral_rows", P(raw), dtype_code(raw), H, W, C, row_off, slide_H, r0, r1, radius, sigma,
+               sigma_color, mode_code, cval, P(inv_mean), float(pseudoval), P(out), stream())
+    return out
+
+
 def block_mean(img: torch.Tensor, fact: int):
     H, W, C = img.shape
     Ho, Wo = -(-H // fact), -(-W // fact)
@@ -644,6 +685,8 @@ FUSED_USED = {"sample": 0, "assign": 0, "assign_banded": 0, "sample_streamed": 0
 # median paths taken (tests read it): the register selection network or the generic rank search;
 # rows_streamed: bands filtered from a slide that is not resident (stream.MedianBand)
 MEDIAN_USED = {"network": 0, "generic": 0, "rows_streamed": 0}
+# bands of a slide that is not resident filtered by the deferred bilateral (stream.BilateralBand)
+BILATERAL_USED = {"rows_streamed": 0}
 
 
 def defer_blur(H: int, W: int, C: int) -> bool:

@@ -24,11 +24,15 @@ Here:
   row window: mw_blur_sample_rows / mw_blur_assign_rows; the non-zero sums of
   integer slides are exact integers), so a streamed slide gives bit for bit
   the resident slide's results (tests/test_gpu_stream.py);
-* a deferred filter is a band filter (``GaussianBand``, ``MedianBand``: the
-  halo it needs and the fp32 rows of a band): the subsample, the label pass
-  and the QC sums run the same loops over either.  The median is an exact
-  selection over a row window (mw_median_rows), so it streams bit for bit
-  too (tests/test_gpu_median_stream.py).
+* a deferred filter is a band filter (``GaussianBand``, ``MedianBand``,
+  ``BilateralBand``: the halo it needs and the fp32 rows of a band): the
+  subsample, the label pass and the QC sums run the same loops over any.  The
+  median is an exact selection over a row window (mw_median_rows), so it
+  streams bit for bit too (tests/test_gpu_median_stream.py); the bilateral
+  visits a pixel's taps in one order whichever tile or band computes it
+  (mw_bilateral_rows), and the whole-slide numbers it needs come from
+  ``image_moments``, whose bits do not depend on the bands
+  (tests/test_gpu_bilateral_stream.py).
 
 Sources (``RowSource``): ``DeviceSource`` (a resident tensor; its bands are
 views, no copy), ``HostSource`` (a host array: pinned memory -- e.g.
@@ -542,15 +546,39 @@ class MedianBand:
         return D.as_float32(D.median_rows(raw, self.size, a, H, y0 - a, y1 - a))
 
 
+class BilateralBand:
+    """The deferred bilateral (``img._pending_bilateral``: sigma, the resolved
+    sigma_color, win_size, mode, cval) as a band filter: halo = the window's
+    radius, a pending log_normalize is the kernel's fused load, and the band's
+    rows come out of mw_bilateral_rows straight into the band buffer.  The
+    constant-image rule was settled by ``img.bilateral_filter`` from the
+    whole slide's minimum and maximum before the filter was deferred."""
+
+    def __init__(self, pending, inv_mean=None, pseudoval: float = 1.0):
+        self.sigma, self.sigma_color, self.win_size, self.mode, self.cval = pending
+        self.inv_mean, self.pseudoval = inv_mean, pseudoval
+        self.halo = D.bilateral_args(self.sigma, self.sigma_color, self.win_size, self.mode, self.cval)[2]
+        self.streamed = False  # the bands come from a slide that is not resident (set by the pass)
+
+    def rows(self, raw, a, y0, y1, H, out_f32):
+        if self.streamed:
+            D.BILATERAL_USED["rows_streamed"] += 1
+        return D.bilateral_rows(raw, self.sigma, self.sigma_color, a, H, y0 - a, y1 - a, win_size=self.win_size,
+                                mode=self.mode, cval=self.cval, inv_mean=self.inv_mean, pseudoval=self.pseudoval,
+                                out=out_f32[:y1 - y0])
+
+
 def band_filter(image):
-    """The band filter of an ``img`` whose filter is deferred (Gaussian or
-    median, with the pending log_normalize as its prologue / epilogue), else
-    None."""
+    """The band filter of an ``img`` whose filter is deferred (Gaussian,
+    median or bilateral, with the pending log_normalize as its prologue /
+    epilogue), else None."""
     inv, p = image._pending if image._pending is not None else (None, 1.0)
     if image._pending_blur is not None:
         return GaussianBand(image._pending_blur[0], inv, p, image._pending_blur[1])
     if image._pending_median is not None:
         return MedianBand(image._pending_median, inv, p)
+    if image._pending_bilateral is not None:
+        return BilateralBand(image._pending_bilateral, inv, p)
     return None
 
 
@@ -656,3 +684,48 @@ def median_gather(src, size, inv_mean, pseudoval: float, feat: torch.Tensor, idx
     if band_rows is None:
         band_rows = band_rows_for(src, src.W * src.C * 4)
     return _band_gather(src, MedianBand(size, inv_mean, pseudoval), feat, idx, r2p, X_out, band_rows)
+
+
+def bilateral_gather(src, pending, inv_mean, pseudoval: float, feat: torch.Tensor, idx: torch.Tensor, r2p,
+                     X_out: torch.Tensor, band_rows=None) -> bool:
+    """X_out[j] = bilateral(lognorm(slide))[pixel of rank idx[j], feat] without
+    storing the filtered slide (``img.subsample_pixels`` after a deferred
+    bilateral, ``pending`` = ``img._pending_bilateral``): per band the filter
+    over the band's output rows (mw_bilateral_rows) and the sampled pixels
+    copied out; there is no fused sample epilogue (the kernel's one thread per
+    pixel does not get cheaper when a fifth of the pixels is sampled).  A
+    resident slide is banded too: its filtered copy is what may not be held."""
+    src = as_source(src)
+    if band_rows is None:
+        band_rows = band_rows_for(src, src.W * src.C * 4)
+    return _band_gather(src, BilateralBand(pending, inv_mean, pseudoval), feat, idx, r2p, X_out, band_rows)
+
+
+def image_moments(src, inv_mean=None, pseudoval: float = 1.0, m2: bool = True, band_rows=None) -> np.ndarray:
+    """Host float64 [n, mean, sum (a - mean)^2, min, max] of the slide ``a`` =
+    ``src`` as fp32, log-normalised when ``inv_mean`` is given, read band by
+    band (mw_image_moments_rows).  The bits do not depend on the band height
+    or on where the slide lives: every slide row is reduced by one workgroup
+    into its entry of a slide_H-long table, which one workgroup reduces by a
+    fixed tree.  Two reads of the slide (the sums, minimum and maximum; then
+    the squared deviations from the mean); ``m2=False`` makes the first only
+    and leaves NaN in the second moment.  They differ from
+    ``device.image_moments`` in the fp64 summation order.  Synchronises on the
+    result."""
+    src = as_source(src)
+    H, W, C = src.shape
+    D._check_inv_mean("image_moments", inv_mean, C)
+    if band_rows is None:
+        band_rows = H if src.zero_copy else band_rows_for(src)
+    dev = D.device()
+    out = torch.empty(5, dtype=torch.float64, device=dev)
+    ws = torch.empty(N.query("mw_image_moments_rows_ws_bytes", H), dtype=torch.uint8, device=dev)
+    for pass_ in (0, 1) if m2 else (0,):
+        for y0, y1, a, raw in bands(src, band_rows, 0):
+            if not raw.is_contiguous():
+                raise ValueError("image_moments: the rows must be contiguous")
+            with profiling.timed("image_moments", (y1 - y0) * src.row_bytes):
+                N.call("mw_image_moments_rows", D.P(raw), D.dtype_code(raw), y1 - y0, W, C, y0, H, pass_,
+                       D.P(inv_mean), float(pseudoval), D.P(ws), D.stream())
+        N.call("mw_image_moments_rows_final", H, W, C, pass_, D.P(ws), D.P(out), D.stream())
+    return D.d2h(out)
