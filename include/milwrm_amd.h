@@ -56,6 +56,9 @@ const char* mw_last_error(void);
  * buffers are sized from it.  Fixed per n (not per device) so results are
  * identical across runs and shard layouts. */
 int mw_stream_blocks(int64_t n);
+/* Rows of each of those workgroups (whole 256-row tiles): block b of the
+ * gather's and mw_col_stats_rows' records covers rows [b * R, (b + 1) * R). */
+int64_t mw_rows_per_block(int64_t n);
 
 /* ---- img.calculate_non_zero_mean (MxIF.py:519-541) --------------------------
  * HWC image of n_pix pixels x C channels.  Outputs per channel: sum of the
@@ -374,6 +377,34 @@ size_t mw_kpp_ws_bytes(int64_t S, int T);
 int mw_kpp_init(const float* d_X, int64_t S, int F, const double* d_mu,
                 const double* d_inv, const float* d_center_row, int T, void* d_ws,
                 void* stream);
+/* mw_kpp_init and step 1 (mw_kpp_step with c = 1, draws h_u[T]) without the
+ * init's pass over the rows, for rows whose producer left per-block moment
+ * records (mw_gather_rows* / mw_col_stats_rows: [n, mean[F], M2[F], max|x|[F]]
+ * fp64 per block of rows_per_block consecutive rows; mw_rows_per_block).  X is
+ * n_seg <= 16 segments in row order (one per gathered image), h_segs a host
+ * array; each segment's records stay valid until the stream has run the call.
+ * The sum of d(x, c0) over a block comes from its record, step 1's targets are
+ * located in the scan of those sums and only the located blocks' rows are read;
+ * step 1's pass takes cur = d(x, c0) from the row it holds.  The workspace
+ * after the call (cur, block and tile sums, candidates) is bit for bit what
+ * mw_kpp_init followed by mw_kpp_step(c = 1) leave when both locate the same
+ * candidate rows; the record sums differ from the summed distances by
+ * rounding, so a target within that rounding of a block boundary may land on
+ * the neighbouring row.  Go on with mw_kpp_step for c = 2.. and
+ * mw_kpp_indices. */
+typedef struct mw_kpp_seg {
+  int64_t row_start;       /* first row of the segment in X */
+  int64_t n_rows;
+  int64_t rows_per_block;  /* rows per record (the last block may be short) */
+  const double* d_records; /* ceil(n_rows / rows_per_block) records of 1 + 3 F fp64 (device) */
+} mw_kpp_seg;
+int mw_kpp_init_moments(const float* d_X, int64_t S, int F, const double* d_mu, const double* d_inv,
+                        const float* d_center_row, const double* h_u, int T, int n_seg,
+                        const mw_kpp_seg* h_segs, void* d_ws, void* stream);
+/* byte offsets of the workspace's sections and its grid, for tests: out[7] =
+ * cur, block sums, tile sums, moment block sums (then their scan), blocks,
+ * tiles, capacity in moment blocks */
+void mw_kpp_ws_sections(int64_t S, int T, int64_t* out);
 /* single-device step for center c (1..k-1); h_u = the T uniform draws */
 int mw_kpp_step(const float* d_X, int64_t S, int F, const double* d_mu,
                 const double* d_inv, int c, const double* h_u, int T,
@@ -534,6 +565,16 @@ int mw_kmeans_fit_async(const float* d_X, int64_t S, int F, const double* h_mu,
                         uint8_t* d_labels, double* h_centers, int* h_n_iter, int64_t* h_init_idx,
                         void* d_ws, size_t ws_bytes, double* h_final_rec, int* h_inertia_exp,
                         void* stream);
+/* mw_kmeans_fit_async for rows that come with their producer's moment records
+ * (h_segs[n_seg], see mw_kpp_init_moments): a k-means++ seeding of k >= 2
+ * centers then starts with mw_kpp_init_moments instead of the init pass; the
+ * same indices, centers, labels and inertia.  n_seg = 0: mw_kmeans_fit_async. */
+int mw_kmeans_fit_async_moments(const float* d_X, int64_t S, int F, const double* h_mu,
+                                const double* h_inv, const double* h_feature_var, const float* h_xmax,
+                                int k, const double* h_init, uint32_t seed, int max_iter, double tol,
+                                uint8_t* d_labels, double* h_centers, int* h_n_iter, int64_t* h_init_idx,
+                                void* d_ws, size_t ws_bytes, double* h_final_rec, int* h_inertia_exp,
+                                int n_seg, const mw_kpp_seg* h_segs, void* stream);
 
 /* ---- batched fits: the find_optimal_k sweep's Lloyd iterations ----------------
  * Replaces kMeansRes' per-k `KMeans(n_clusters=k, random_state=seed).fit(X)`

@@ -649,6 +649,7 @@ class mxif_labeler(tissue_labeler):
         paths = []
         totals = []
         draws = []  # (row offset, rows, rank draws, rank base): the rows' slide order, for a spatial row sort
+        moments = []  # (row offset, rows, rows per block, records): the gathers' per-block moments
         rank_base = 0
         for n_img, (im, batch, (r2p, M), S) in enumerate(
                 zip(images, self.image_df["batch_names"], ranks, counts)):
@@ -669,12 +670,17 @@ class mxif_labeler(tissue_labeler):
                         D.rank_to_pixel(idx, r2p)
                 totals.append((tot, S))
                 feat = D.h2d(np.asarray(im._features(features), dtype=np.int32), dev)
+                # the per-block moment records stay with the rows: k-means++
+                # takes its first step's block potentials from them
+                # (DeviceRows.moments)
                 if _gather_deferred(im, feat, idx, r2p, X[off:off + S]):
-                    D.col_stats_rows(X[off:off + S], img_stats[n_img], accumulate=False,
-                                     absmax=xmax)
+                    rec = D.col_stats_rows(X[off:off + S], img_stats[n_img], accumulate=False,
+                                           absmax=xmax, keep_records=True)
                 else:
-                    D.gather_rows(D.as_float32(im._materialize()), feat, idx, None if px else r2p,
-                                  X[off:off + S], img_stats[n_img], accumulate=False, absmax=xmax)
+                    rec = D.gather_rows(D.as_float32(im._materialize()), feat, idx, None if px else r2p,
+                                        X[off:off + S], img_stats[n_img], accumulate=False, absmax=xmax,
+                                        keep_records=True)
+                moments.append((off, S) + rec)
                 # slide-order keys: pixels or ranks (both monotone in the pixel)
                 # past the previous images' pixel counts
                 draws.append((off, S, idx, rank_base))
@@ -706,6 +712,7 @@ class mxif_labeler(tissue_labeler):
         self._rows = DeviceRows(X, mu, inv, feature_var=self.scaler.var_ * inv * inv,
                                 xmax_local=host[1])
         self._rows.draws = draws
+        self._rows.moments = moments
         self._cluster_host = None
 
     def _image_list(self):

@@ -33,6 +33,7 @@ _PROTOS = {
     "mw_host_f32_to_f64": (c_i32, [c_vp, c_i64, c_vp, c_i32]),
     "mw_last_error": (C.c_char_p, []),
     "mw_stream_blocks": (c_i32, [c_i64]),
+    "mw_rows_per_block": (c_i64, [c_i64]),
     "mw_nz_stats_ws_bytes": (c_sz, [c_i64, c_i32]),
     "mw_nz_stats": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mw_lognorm": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
@@ -74,6 +75,8 @@ _PROTOS = {
     "mw_legacy_randint_from_states": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mw_kpp_ws_bytes": (c_sz, [c_i64, c_i32]),
     "mw_kpp_init": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "mw_kpp_init_moments": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "mw_kpp_ws_sections": (None, [c_i64, c_i32, c_vp]),
     "mw_kpp_step": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "mw_kpp_indices": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "mw_kpp_step_fold": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp,
@@ -97,6 +100,9 @@ _PROTOS = {
                               C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mw_kmeans_fit_async": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_u32, c_i32,
                                     C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mw_kmeans_fit_async_moments": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_u32, c_i32,
+                                            C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_i32,
+                                            c_vp, c_vp]),
     "mw_lloyd_fits": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, C.c_double,
                               c_i32, c_i32, C.c_double, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
@@ -151,6 +157,11 @@ class LloydFit(C.Structure):
     _fields_ = [("centers", c_vp), ("drift", c_vp), ("half_sep", c_vp), ("labels", c_vp),
                 ("ub", c_vp), ("lb", c_vp), ("ws", c_vp), ("out", c_vp), ("k", c_i32),
                 ("drift_max", c_f32), ("inertia_exp", c_i32)]
+
+
+class KppSeg(C.Structure):
+    """``mw_kpp_seg`` (include/milwrm_amd.h)."""
+    _fields_ = [("row_start", c_i64), ("n_rows", c_i64), ("rows_per_block", c_i64), ("d_records", c_vp)]
 
 
 # mw_fit_comm's collectives (include/milwrm_amd.h): all_reduce_sum(ctx, off, n,

@@ -409,7 +409,8 @@ static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_m
                            const double* h_feature_var, const float* h_xmax, int k, const double* h_init,
                            uint32_t seed, int max_iter, double tol, uint8_t* d_labels, double* h_centers,
                            double* h_inertia, int* h_n_iter, int64_t* h_init_idx, void* d_ws, size_t ws_bytes,
-                           double* h_final_rec, int* h_inertia_exp, void* stream);
+                           double* h_final_rec, int* h_inertia_exp, void* stream, int n_seg = 0,
+                           const mw_kpp_seg* h_segs = nullptr);
 
 // per pass of the thread's last single fit: kind, changed, recomputed, rows read
 static thread_local std::vector<int64_t> fit_hist;
@@ -444,11 +445,27 @@ extern "C" int mw_kmeans_fit_async(const float* d_X, int64_t S, int F, const dou
                          h_inertia_exp, stream);
 }
 
+extern "C" int mw_kmeans_fit_async_moments(const float* d_X, int64_t S, int F, const double* h_mu,
+                                           const double* h_inv, const double* h_feature_var,
+                                           const float* h_xmax, int k, const double* h_init, uint32_t seed,
+                                           int max_iter, double tol, uint8_t* d_labels, double* h_centers,
+                                           int* h_n_iter, int64_t* h_init_idx, void* d_ws, size_t ws_bytes,
+                                           double* h_final_rec, int* h_inertia_exp, int n_seg,
+                                           const mw_kpp_seg* h_segs, void* stream) {
+  MW_CHECK_ARG(h_final_rec && h_inertia_exp, "mw_kmeans_fit_async_moments: null final-record pointer");
+  MW_CHECK_ARG(n_seg == 0 || h_segs, "mw_kmeans_fit_async_moments: null segments");
+  double unused = 0.0;
+  return kmeans_fit_impl(d_X, S, F, h_mu, h_inv, h_feature_var, h_xmax, k, h_init, seed, max_iter, tol,
+                         d_labels, h_centers, &unused, h_n_iter, h_init_idx, d_ws, ws_bytes, h_final_rec,
+                         h_inertia_exp, stream, n_seg, h_segs);
+}
+
 static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_mu, const double* h_inv,
                            const double* h_feature_var, const float* h_xmax, int k, const double* h_init,
                            uint32_t seed, int max_iter, double tol, uint8_t* d_labels, double* h_centers,
                            double* h_inertia, int* h_n_iter, int64_t* h_init_idx, void* d_ws, size_t ws_bytes,
-                           double* h_final_rec, int* h_inertia_exp, void* stream) {
+                           double* h_final_rec, int* h_inertia_exp, void* stream, int n_seg,
+                           const mw_kpp_seg* h_segs) {
   MW_CHECK_ARG(d_X && h_mu && h_inv && d_labels && h_centers && h_inertia && h_n_iter,
                "mw_kmeans_fit: null pointer");
   MW_CHECK_ARG(F >= 1 && F <= 64, "mw_kmeans_fit: F=%d outside [1, 64]", F);
@@ -586,9 +603,17 @@ static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_m
     LegacyRandom rs(seed);
     const double u0 = rs.sample();
     const int64_t first = first_center_index(S, u0);
-    MW_TRY(mw_kpp_init(d_X, S, F, d_mu, d_inv, d_X + first * F, T, big, st));
+    // rows with their producer's moment records: step 1's block potentials
+    // from the records, no init pass (kpp.hip mw_kpp_init_moments)
+    const bool moments = n_seg > 0 && k >= 2;
     std::vector<double> u(T);
-    for (int c = 1; c < k; ++c) {
+    if (moments) {
+      for (int t = 0; t < T; ++t) u[t] = rs.sample();
+      MW_TRY(mw_kpp_init_moments(d_X, S, F, d_mu, d_inv, d_X + first * F, u.data(), T, n_seg, h_segs, big, st));
+    } else {
+      MW_TRY(mw_kpp_init(d_X, S, F, d_mu, d_inv, d_X + first * F, T, big, st));
+    }
+    for (int c = moments ? 2 : 1; c < k; ++c) {
       for (int t = 0; t < T; ++t) u[t] = rs.sample();
       if (fold && c == k - 1)
         MW_TRY(mw_kpp_step_fold(d_X, S, F, d_mu, d_inv, c, u.data(), T, big, first, fit.a32, fit.b32, fit.qexp,

@@ -18,6 +18,18 @@
 //     selection (argmin, first wins) and the target positions, as before.
 // Single device: mw_kpp_init, then per step mw_kpp_step (selection + search
 // kernel, candidate table, pass), mw_kpp_indices; no host round trip.
+// Rows that come with their producer's per-block moment records (the
+// subsample gather's Chan records, kept for the scaler anyway) skip the init
+// pass: mw_kpp_init_moments takes the sum of d(x, c0) over each record's block
+// from the record (kpp_mom_sums_kernel: sum_f inv_f^2 (M2_f + n (mean_f -
+// c0_f)^2), and the scan), locates step 1's T targets in that scan, recomputes
+// d(x, c0) only over the T located blocks (kpp_mom_tiles_kernel: their tile
+// sums; kpp_mom_search_kernel: tile, then row, by kpp_find_row like every
+// step's search) and runs step 1's pass in MODE 3, which takes cur = d(x, c0)
+// from the row it holds.  From that pass on every sum comes from the same
+// per-row values as after mw_kpp_init + mw_kpp_step(1): the same bits.  The
+// moment sums only choose the block (they differ from the summed distances
+// by rounding, as the block prefix differs from a sequential cumsum).
 // Row-sharded (milwrm_amd/dist.py DistComm.kpp): mw_kpp_pots, host argmin and
 // target ownership, mw_kpp_search, host all-reduce of the candidate rows,
 // mw_kpp_trial.  The block grid (kblocks/krows) and every summation order are
@@ -41,8 +53,12 @@ static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 //   tsum  [2][T][NTL] fp64         per-64-row-tile trial sums (same)
 //   tab   [2][kKppTab] fp64        candidate tables (same)
 //   st    cand[T] i64, chosen[256] i64, best i32
+//   mom   msum[kMomBlocks] | mscan[kMomBlocks] fp64   sums of d(x, c0) per
+//         moment block and their scan (mw_kpp_init_moments)
+constexpr int kMomSegs = 16;       // segments (images) of one X with moment records
+constexpr int kMomBlocks = 16384;  // their blocks (<= 1024 per segment)
 struct KppLayout {
-  size_t cur, bsum, tsum, tab, st, total;
+  size_t cur, bsum, tsum, tab, st, mom, total;
   int G;
   int64_t NTL;
 };
@@ -55,13 +71,14 @@ static KppLayout kpp_layout(int64_t S, int T) {
   L.tsum = al256(L.bsum + 2 * (size_t)T * L.G * sizeof(double));
   L.tab = al256(L.tsum + 2 * (size_t)T * L.NTL * sizeof(double));
   L.st = al256(L.tab + 2 * (size_t)kKppTabBytes);
-  L.total = al256(L.st + (size_t)(T + 256) * sizeof(int64_t) + 64);
+  L.mom = al256(L.st + (size_t)(T + 256) * sizeof(int64_t) + 64);
+  L.total = al256(L.mom + 2 * (size_t)kMomBlocks * sizeof(double));
   return L;
 }
 
 struct KppPtrs {
   KppLayout L;
-  double *cur, *bsum, *tsum, *tab;
+  double *cur, *bsum, *tsum, *tab, *msum, *mscan;
   int64_t *cand, *chosen;
   int* best;
   double* bsum_of(int c, int T) const { return bsum + (size_t)(c & 1) * T * L.G; }
@@ -79,6 +96,8 @@ static KppPtrs kpp_ptrs(const void* d_ws, int64_t S, int T) {
   p.cand = reinterpret_cast<int64_t*>(base + p.L.st);
   p.chosen = p.cand + T;
   p.best = reinterpret_cast<int*>(p.chosen + 256);
+  p.msum = reinterpret_cast<double*>(base + p.L.mom);
+  p.mscan = p.msum + kMomBlocks;
   return p;
 }
 
@@ -168,7 +187,7 @@ __device__ __forceinline__ void kpp_row_dists(const float* __restrict__ xr, int 
   auto feat = [&](double xv, int f) {  // past F: inv = mi = c = 0, exact zeros
     const double xs = fma(xv, tb[f], -tb[576 + f]);
     xx = fma(xs, xs, xx);
-    if (MODE == 2) dotp = fma(xs, tp[f * 8], dotp);
+    if (MODE >= 2) dotp = fma(xs, tp[f * 8], dotp);
 #pragma unroll
     for (int c = 0; c < T; ++c) dot[c] = fma(xs, tb[64 + f * 8 + c], dot[c]);
   };
@@ -187,13 +206,13 @@ __device__ __forceinline__ void kpp_row_dists(const float* __restrict__ xr, int 
       r.mi = tb[576 + g];
 #pragma unroll
       for (int c = 0; c < T; ++c) r.c[c] = tb[64 + g * 8 + c];
-      r.pend = MODE == 2 ? tp[g * 8] : 0.0;
+      r.pend = MODE >= 2 ? tp[g * 8] : 0.0;
       return r;
     };
     auto featt = [&](double xv, const TabF& q) {
       const double xs = fma(xv, q.inv, -q.mi);
       xx = fma(xs, xs, xx);
-      if (MODE == 2) dotp = fma(xs, q.pend, dotp);
+      if (MODE >= 2) dotp = fma(xs, q.pend, dotp);
 #pragma unroll
       for (int c = 0; c < T; ++c) dot[c] = fma(xs, q.c[c], dot[c]);
     };
@@ -215,7 +234,7 @@ __device__ __forceinline__ void kpp_row_dists(const float* __restrict__ xr, int 
     const double e = fma(-2.0, dot[c], xx) + tb[640 + c];
     d[c] = e > 0.0 ? e : 0.0;
   }
-  if (MODE == 2) {
+  if (MODE >= 2) {
     const double e = fma(-2.0, dotp, xx) + tcc;
     dp = e > 0.0 ? e : 0.0;
   }
@@ -223,7 +242,11 @@ __device__ __forceinline__ void kpp_row_dists(const float* __restrict__ xr, int 
 
 // The pass.  MODE 0 (init, T = 1): cur = d(x, c0).  MODE 1 (step 1): cur as
 // is.  MODE 2 (steps >= 2): cur = min(cur, d(x, pending)), the pending
-// center being column `best` of the previous step's table.  Then the trial
+// center being column `best` of the previous step's table.  MODE 3 (step 1
+// after the init from moments): cur = d(x, c0), c0 being the pending center
+// (column 0 of the init's table): no cur load, and MODE 0's operations on the
+// row the pass holds anyway, so cur, and with it every sum of the step, has
+// the bits of MODE 0 followed by MODE 1.  Then the trial
 // values m_t = min(cur, d(x, cand_t)): their sums per tile (wave sum) and per
 // block (lanes over their tiles, then the block sum).  Waves stream 64-row
 // tiles (buffer loads, next tile and its cur in flight) transposed through
@@ -256,7 +279,8 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
   const int ntile = hi > lo ? (int)((hi - lo + 63) / 64) : 0;
   const int64_t total = S * (int64_t)F, n4 = total >> 2;
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(X + lo * F, (S - lo) * F * 4);
-  const __amdgpu_buffer_rsrc_t rc = make_rsrc(cur + lo, MODE == 0 ? 0 : (hi - lo) * 8);
+  constexpr bool LOADS_CUR = MODE == 1 || MODE == 2;
+  const __amdgpu_buffer_rsrc_t rc = make_rsrc(cur + lo, LOADS_CUR ? (hi - lo) * 8 : 0);
   const int tile_bytes = 64 * F * 4;
   double acc[T];
 #pragma unroll
@@ -270,12 +294,12 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
   const double* tb = tab;
   const int pb = MODE == 2 ? (best ? *best : best_val) : 0;
   const double* tp = tab_prev + 64 + pb;
-  const double tcc = MODE == 2 ? tab_prev[640 + pb] : 0.0;
+  const double tcc = MODE >= 2 ? tab_prev[640 + pb] : 0.0;
   f4v v[NV];
   double cur_next = 0.0;
   auto fetch = [&](int tt) {
     tt = tt < ntile ? tt : ntile - 1;
-    if (MODE != 0)
+    if (LOADS_CUR)
       cur_next = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rc, lane * 8, tt * 512, kStreamAux));
 #pragma unroll
     for (int i = 0; i < NV; ++i)  // only the vectors that hold the tile's 64 x F floats
@@ -309,7 +333,7 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
     auto feat = [&](double xv, int f) {  // past F: inv = mi = c = 0, exact zeros
       const double xs = fma(xv, tb[f], -tb[576 + f]);
       xx = fma(xs, xs, xx);
-      if (MODE == 2) dotp = fma(xs, tp[f * 8], dotp);
+      if (MODE >= 2) dotp = fma(xs, tp[f * 8], dotp);
 #pragma unroll
       for (int c = 0; c < T; ++c) dot[c] = fma(xs, tb[64 + f * 8 + c], dot[c]);
     };
@@ -328,13 +352,13 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
         r.mi = tb[576 + g];
 #pragma unroll
         for (int c = 0; c < T; ++c) r.c[c] = tb[64 + g * 8 + c];
-        r.pend = MODE == 2 ? tp[g * 8] : 0.0;
+        r.pend = MODE >= 2 ? tp[g * 8] : 0.0;
         return r;
       };
       auto featt = [&](double xv, const TabF& q) {
         const double xs = fma(xv, q.inv, -q.mi);
         xx = fma(xs, xs, xx);
-        if (MODE == 2) dotp = fma(xs, q.pend, dotp);
+        if (MODE >= 2) dotp = fma(xs, q.pend, dotp);
 #pragma unroll
         for (int c = 0; c < T; ++c) dot[c] = fma(xs, q.c[c], dot[c]);
       };
@@ -371,7 +395,7 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
       const double e = fma(-2.0, dot[c], xx) + tb[640 + c];
       d[c] = e > 0.0 ? e : 0.0;
     }
-    if (MODE == 2) {
+    if (MODE >= 2) {
       const double e = fma(-2.0, dotp, xx) + tcc;
       dp = e > 0.0 ? e : 0.0;
     }
@@ -380,6 +404,7 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
     const int64_t row = r0 + lane;
     if (MODE == 0) cd = d[0];
     if (MODE == 2) cd = cd < dp ? cd : dp;
+    if (MODE == 3) cd = dp;
     if (MODE != 1 && valid) cur[row] = cd;
     double mv[T];
 #pragma unroll
@@ -726,6 +751,188 @@ __global__ void __launch_bounds__(1024) kpp_pots_kernel(const double* __restrict
   }
 }
 
+// One wave: the first row of the block [lo, hi) at which base + the running
+// sum of the rows' values reaches rv (lane 0's return value; the block's last
+// row when rounding lets none reach it).  ts[i] = the sum of tile i (rows
+// lo + 64 i ...), val(row) = the value of a row, s_row = 64 doubles of LDS.
+template <typename ValFn>
+__device__ __forceinline__ int64_t kpp_find_row(int64_t lo, int64_t hi, const double* __restrict__ ts,
+                                                double base, double rv, int lane, double* s_row, ValFn val) {
+  int64_t idx = hi - 1;  // rounding fallback: the block's last row
+  // chunked scan of the block's tile sums: lane l owns tiles [l*per, ...)
+  const int64_t ntl = (hi - lo + 63) >> 6;
+  const int64_t per = (ntl + 63) / 64;
+  const int64_t c_lo = lane * per, c_hi = min(ntl, c_lo + per);
+  double part = 0.0;
+  for (int64_t i = c_lo; i < c_hi; ++i) part += ts[i];
+  double incl = part;
+  for (int o = 1; o < 64; o <<= 1) {
+    const double v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  double excl = __shfl_up(incl, 1, 64);
+  if (lane == 0) excl = 0.0;
+  const bool hit = c_lo < c_hi && base + incl >= rv && (lane == 0 || base + excl < rv);
+  const uint64_t mask = __ballot(hit);
+  if (mask) {
+    const int q = __builtin_ctzll(mask);
+    // the tile inside chunk q (sequential over its tiles)
+    const int64_t q_lo = q * per, q_hi = min(ntl, q_lo + per);
+    double r2 = base + __shfl(excl, q, 64);
+    int64_t tile = q_hi - 1;
+    for (int64_t i = q_lo; i < q_hi; ++i) {
+      if (r2 + ts[i] >= rv) { tile = i; break; }
+      r2 += ts[i];
+    }
+    // r2 = prefix before `tile` (or before the chunk's last tile on fallback)
+    if (tile == q_hi - 1) {
+      r2 = base + __shfl(excl, q, 64);
+      for (int64_t i = q_lo; i < tile; ++i) r2 += ts[i];
+    }
+    // the tile's values, recomputed, then the first row reaching rv
+    const int64_t r0 = lo + tile * 64, row = r0 + lane;
+    s_row[lane] = row < hi ? val(row) : 0.0;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (lane == 0) {
+      const int nrow = (int)min((int64_t)64, hi - r0);
+      idx = r0 + nrow - 1;
+      double r = r2;
+      for (int i = 0; i < nrow; ++i) {
+        r += s_row[i];
+        if (r >= rv) { idx = r0 + i; break; }
+      }
+    }
+  }
+  return idx;
+}
+
+// ---- step 1 from the gather's moments (mw_kpp_init_moments) ---------------
+// The rows of X come in segments (one per image) whose producer left a Chan
+// record [n, mean[F], M2[F], max|x|[F]] per block of R consecutive rows.  In
+// scaled space the sum over a block's rows of |x' - c0'|^2 is
+//   sum_f inv_f^2 (M2_f + n (mean_f - c0_f)^2),
+// so the block level of step 1's search needs no pass over the rows; only the
+// T located blocks have their rows' distances recomputed.
+struct KppMom {
+  int n;                     // segments
+  int nb[kMomSegs + 1];      // first moment block of each segment, total at [n]
+  int64_t start[kMomSegs], rows[kMomSegs], R[kMomSegs];
+  const double* rec[kMomSegs];
+};
+
+// one sum per moment block (features in order) and their inclusive scan
+// (1024 blocks at a time, scan_blocks' order, the carry added last)
+__global__ void __launch_bounds__(1024) kpp_mom_sums_kernel(KppMom m, int F, const double* __restrict__ inv,
+                                                            const float* __restrict__ c0,
+                                                            double* __restrict__ msum,
+                                                            double* __restrict__ mscan) {
+  __shared__ double s[1024];
+  const int t = threadIdx.x, NB = m.nb[m.n];
+  double carry = 0.0;
+  for (int b0 = 0; b0 < NB; b0 += 1024) {
+    const int b = b0 + t;
+    double v = 0.0;
+    if (b < NB) {
+      const double* rp = m.rec[0];
+      int first = 0;
+#pragma unroll
+      for (int i = 1; i < kMomSegs; ++i)
+        if (i < m.n && b >= m.nb[i]) { rp = m.rec[i]; first = m.nb[i]; }
+      const double* r = rp + (size_t)(b - first) * (1 + 3 * F);
+      const double nrow = r[0];
+      for (int f = 0; f < F; ++f) {
+        const double dm = r[1 + f] - (double)c0[f], iv = inv[f];
+        v = fma(iv * iv, fma(nrow * dm, dm, r[1 + F + f]), v);
+      }
+      msum[b] = v;
+    }
+    __syncthreads();
+    s[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const double a = t >= o ? s[t - o] : 0.0;
+      __syncthreads();
+      s[t] += a;
+      __syncthreads();
+    }
+    if (b < NB) mscan[b] = carry + s[t];
+    carry += s[1023];
+  }
+}
+
+// a target's moment block: rv = u * (the last scan entry), the first block
+// whose scan entry reaches it (else the last block), its rows [lo, hi) and
+// the scan before it.  One wave; every lane returns the same values.
+struct KppMomLoc {
+  int64_t lo, hi;
+  double base, rv;
+};
+__device__ __forceinline__ KppMomLoc kpp_mom_locate(const KppMom& m, const double* __restrict__ mscan,
+                                                    double u, int lane) {
+  const int NB = m.nb[m.n];
+  KppMomLoc L;
+  L.rv = u * mscan[NB - 1];
+  int blk = NB - 1;
+  for (int i = lane; i < NB; i += 64) {
+    const double prev = i > 0 ? mscan[i - 1] : 0.0;
+    if (mscan[i] >= L.rv && (i == 0 || prev < L.rv)) blk = min(blk, i);
+  }
+  for (int o = 32; o > 0; o >>= 1) blk = min(blk, __shfl_xor(blk, o, 64));
+  L.base = blk > 0 ? mscan[blk - 1] : 0.0;
+  int first = 0;
+  int64_t st = m.start[0], nr = m.rows[0], R = m.R[0];
+#pragma unroll
+  for (int i = 1; i < kMomSegs; ++i)
+    if (i < m.n && blk >= m.nb[i]) { first = m.nb[i]; st = m.start[i]; nr = m.rows[i]; R = m.R[i]; }
+  L.lo = st + (int64_t)(blk - first) * R;
+  L.hi = min(st + nr, L.lo + R);
+  return L;
+}
+
+struct KppU8 { double u[8]; };
+
+// the tile sums of d(x, c0) over each target's located block (target
+// blockIdx.y, tile i = rows lo + 64 i ... of the block, the grid's waves over
+// the tiles): kpp_dist_row's values, the pass's bits
+__global__ void __launch_bounds__(256) kpp_mom_tiles_kernel(const float* __restrict__ X, int F,
+                                                            const double* __restrict__ tab0, KppMom m,
+                                                            const double* __restrict__ mscan, KppU8 us,
+                                                            int64_t NTL, double* __restrict__ tsum0) {
+  const int lane = threadIdx.x & 63, w = blockIdx.y;
+  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+  const KppMomLoc L = kpp_mom_locate(m, mscan, us.u[w], lane);
+  const int64_t ntl = (L.hi - L.lo + 63) >> 6;
+  double* ts = tsum0 + (size_t)w * NTL;
+  for (int64_t i = gw; i < ntl; i += nw) {
+    const int64_t row = L.lo + i * 64 + lane;
+    const double d = row < L.hi ? kpp_dist_row(X + row * F, F, tab0, 0) : 0.0;
+    const double v = wave_sum_lane0(d);
+    if (lane == 0) ts[i] = v;
+  }
+}
+
+// step 1's candidates: one wave per target walks its block's tile sums and
+// the located tile's recomputed values (kpp_find_row, as every later step)
+__global__ void __launch_bounds__(512) kpp_mom_search_kernel(const float* __restrict__ X, int F,
+                                                             const double* __restrict__ tab0, KppMom m,
+                                                             const double* __restrict__ mscan, KppU8 us,
+                                                             int64_t S, int64_t NTL,
+                                                             const double* __restrict__ tsum0,
+                                                             int64_t* __restrict__ cand, int* __restrict__ best) {
+  __shared__ double s_row[8][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (threadIdx.x == 0) *best = 0;  // the array searched: the only one
+  const KppMomLoc L = kpp_mom_locate(m, mscan, us.u[w], lane);
+  int64_t idx = kpp_find_row(L.lo, L.hi, tsum0 + (size_t)w * NTL, L.base, L.rv, lane, s_row[w],
+                             [&](int64_t row) { return kpp_dist_row(X + row * F, F, tab0, 0); });
+  if (lane == 0) {
+    if (idx > S - 1) idx = S - 1;
+    if (idx < 0) idx = 0;
+    cand[w] = idx;
+  }
+}
+
 // Selection of the finished step's best array (argmin of the potentials,
 // first wins; skipped when the host gives it), then the search for this
 // step's T targets (u_t * pot, or the host's local targets, < 0 = not on this
@@ -793,61 +1000,15 @@ __global__ void __launch_bounds__(1024) kpp_search_kernel(
   for (int o = 32; o > 0; o >>= 1) blk = min(blk, __shfl_xor(blk, o, 64));
   const double base = blk > 0 ? s[blk - 1] : 0.0;
   const int64_t lo = (int64_t)blk * R, hi = min(S, lo + R);
-  int64_t idx = hi - 1;  // rounding fallback: the block's last row
-  // 2) chunked scan of the block's tile sums: lane l owns tiles [t0 + l*per, ...)
-  const int64_t t0 = lo >> 6, t1 = (hi + 63) >> 6, ntl = t1 - t0;
-  const int64_t per = (ntl + 63) / 64;
-  const int64_t c_lo = t0 + lane * per, c_hi = min(t1, c_lo + per);
-  const double* ts = tsum_cur + (size_t)b * NTL;
-  double part = 0.0;
-  for (int64_t i = c_lo; i < c_hi; ++i) part += ts[i];
-  double incl = part;
-  for (int o = 1; o < 64; o <<= 1) {
-    const double v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  double excl = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl = 0.0;
-  const bool hit = c_lo < c_hi && base + incl >= rv && (lane == 0 || base + excl < rv);
-  const uint64_t mask = __ballot(hit);
-  if (mask) {
-    const int q = __builtin_ctzll(mask);
-    // 3) the tile inside chunk q (sequential over its tiles)
-    const int64_t q_lo = t0 + q * per, q_hi = min(t1, q_lo + per);
-    double r2 = base + __shfl(excl, q, 64);
-    int64_t tile = q_hi - 1;
-    for (int64_t i = q_lo; i < q_hi; ++i) {
-      if (r2 + ts[i] >= rv) { tile = i; break; }
-      r2 += ts[i];
-    }
-    // r2 = prefix before `tile` (or before the chunk's last tile on fallback)
-    if (tile == q_hi - 1) {
-      r2 = base + __shfl(excl, q, 64);
-      for (int64_t i = q_lo; i < tile; ++i) r2 += ts[i];
-    }
-    // 4) the tile's values, recomputed, then the first row reaching rv
-    const int64_t row = tile * 64 + lane;
-    double a = 0.0;
-    if (row < hi) {
-      a = cur[row];
-      if (has_pend) {
-        const double dp = kpp_dist_row(X + row * F, F, tab_prev, b);
-        a = a < dp ? a : dp;
-      }
-    }
-    s_row[w][lane] = a;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (lane == 0) {
-      const int nrow = (int)min((int64_t)64, hi - tile * 64);
-      idx = tile * 64 + nrow - 1;
-      double r = r2;
-      for (int i = 0; i < nrow; ++i) {
-        r += s_row[w][i];
-        if (r >= rv) { idx = tile * 64 + i; break; }
-      }
-    }
-  }
+  int64_t idx = kpp_find_row(lo, hi, tsum_cur + (size_t)b * NTL + (lo >> 6), base, rv, lane, s_row[w],
+                                   [&](int64_t row) {
+                                     double a = cur[row];
+                                     if (has_pend) {
+                                       const double dp = kpp_dist_row(X + row * F, F, tab_prev, b);
+                                       a = a < dp ? a : dp;
+                                     }
+                                     return a;
+                                   });
   if (lane == 0) {
     if (idx > S - 1) idx = S - 1;
     if (idx < 0) idx = 0;
@@ -859,14 +1020,14 @@ __global__ void __launch_bounds__(1024) kpp_search_kernel(
 static int kpp_pass_launch(const float* X, int64_t S, int F, const double* mu, const double* inv,
                            const KppPtrs& p, int c, const int* best, int best_val,
                            const int64_t* cand, const float* rows, int T, int64_t* chosen_reset,
-                           hipStream_t s) {
+                           hipStream_t s, bool c0_pending = false) {
   double* tab = p.tab_of(c);
   hipLaunchKernelGGL(kpp_prep_kernel, dim3(1), dim3(512), 0, s, X, F, mu, inv, cand, rows, T, tab,
                      chosen_reset);
   MW_LAUNCH_CHECK();
   const int FM = F <= 8 ? 8 : F <= 16 ? 16 : F <= 32 ? 32 : 64;
   const size_t lds = 64 + (size_t)4 * (FM == 64 ? 64 * F + 4 : 64 * FM) * sizeof(float);  // the pass's tiles
-  const int mode = c == 0 ? 0 : c == 1 ? 1 : 2;
+  const int mode = c == 0 ? 0 : c == 1 ? (c0_pending ? 3 : 1) : 2;  // 3: cur = d(x, c0) taken in the pass
   const double* tab_prev = c >= 1 ? p.tab_of(c - 1) : nullptr;
   double* bs = p.bsum_of(c, T);
   double* tsm = p.tsum_of(c, T);
@@ -875,7 +1036,7 @@ static int kpp_pass_launch(const float* X, int64_t S, int F, const double* mu, c
   hipLaunchKernelGGL((kpp_pass_kernel<FMV, TV, MV>), dim3(p.L.G), dim3(256), lds, s, X, S, F, tab, \
                      tab_prev, best, best_val, p.cur, R, p.L.NTL, bs, tsm)
 #define MW_KPM(FMV, TV) \
-  if (mode == 1) MW_KP(FMV, TV, 1); else MW_KP(FMV, TV, 2);
+  if (mode == 1) MW_KP(FMV, TV, 1); else if (mode == 3) MW_KP(FMV, TV, 3); else MW_KP(FMV, TV, 2);
 #define MW_KPT(FMV)                                                                        \
   if (mode == 0) { MW_KP(FMV, 1, 0); }                                                     \
   else switch (T) {                                                                        \
@@ -923,6 +1084,70 @@ int mw_kpp_init(const float* d_X, int64_t S, int F, const double* d_mu, const do
   const KppPtrs p = kpp_ptrs(d_ws, S, T);
   return kpp_pass_launch(d_X, S, F, d_mu, d_inv, p, 0, nullptr, 0, nullptr, d_center_row, 1,
                          p.chosen, as_stream(stream));
+}
+
+void mw_kpp_ws_sections(int64_t S, int T, int64_t* out) {
+  const KppLayout L = kpp_layout(S, T);
+  out[0] = (int64_t)L.cur;
+  out[1] = (int64_t)L.bsum;
+  out[2] = (int64_t)L.tsum;
+  out[3] = (int64_t)L.mom;
+  out[4] = L.G;
+  out[5] = L.NTL;
+  out[6] = kMomBlocks;
+}
+
+int mw_kpp_init_moments(const float* d_X, int64_t S, int F, const double* d_mu, const double* d_inv,
+                        const float* d_center_row, const double* h_u, int T, int n_seg,
+                        const mw_kpp_seg* h_segs, void* d_ws, void* stream) {
+  MW_CHECK_ARG(d_X && d_mu && d_inv && d_ws && d_center_row && h_u && h_segs,
+               "mw_kpp_init_moments: null pointer");
+  MW_CHECK_ARG(S > 0 && F > 0 && F <= 64, "mw_kpp_init_moments: bad shape (F <= 64)");
+  MW_CHECK_ARG(T >= 1 && T <= 8, "mw_kpp_init_moments: n_local_trials must be in [1, 8]");
+  MW_CHECK_ARG(n_seg >= 1 && n_seg <= kMomSegs, "mw_kpp_init_moments: %d segments outside [1, %d]", n_seg,
+               kMomSegs);
+  KppMom m{};
+  m.n = n_seg;
+  int64_t at = 0, nb = 0, rmax = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const mw_kpp_seg& g = h_segs[i];
+    MW_CHECK_ARG(g.d_records && g.n_rows > 0 && g.rows_per_block > 0 && g.row_start == at,
+                 "mw_kpp_init_moments: segment %d is empty or does not follow the one before it", i);
+    m.nb[i] = (int)nb;
+    m.start[i] = g.row_start;
+    m.rows[i] = g.n_rows;
+    m.R[i] = g.rows_per_block;
+    m.rec[i] = g.d_records;
+    at += g.n_rows;
+    nb += (g.n_rows + g.rows_per_block - 1) / g.rows_per_block;
+    MW_CHECK_ARG(nb <= kMomBlocks, "mw_kpp_init_moments: more than %d moment blocks", kMomBlocks);
+    rmax = std::max(rmax, std::min(g.n_rows, g.rows_per_block));
+  }
+  m.nb[n_seg] = (int)nb;
+  MW_CHECK_ARG(at == S, "mw_kpp_init_moments: the segments hold %lld rows, X has %lld", (long long)at,
+               (long long)S);
+  const KppPtrs p = kpp_ptrs(d_ws, S, T);
+  hipStream_t s = as_stream(stream);
+  KppU8 us{};
+  for (int i = 0; i < T; ++i) us.u[i] = h_u[i];
+  // the init's table (column 0 = c0) and the moment blocks' sums and scan
+  double* tab0 = p.tab_of(0);
+  hipLaunchKernelGGL(kpp_prep_kernel, dim3(1), dim3(512), 0, s, d_X, F, d_mu, d_inv,
+                     (const int64_t*)nullptr, d_center_row, 1, tab0, p.chosen);
+  hipLaunchKernelGGL(kpp_mom_sums_kernel, dim3(1), dim3(1024), 0, s, m, F, d_inv, d_center_row, p.msum,
+                     p.mscan);
+  MW_LAUNCH_CHECK();
+  // step 1's targets: block by the moment scan, then the located blocks' rows
+  const int64_t tiles = (rmax + 63) / 64;
+  const int nsub = (int)std::min<int64_t>(64, std::max<int64_t>(1, (tiles + 3) / 4));
+  double* ts0 = p.tsum_of(0, T);
+  hipLaunchKernelGGL(kpp_mom_tiles_kernel, dim3(nsub, T), dim3(256), 0, s, d_X, F, tab0, m, p.mscan, us,
+                     p.L.NTL, ts0);
+  hipLaunchKernelGGL(kpp_mom_search_kernel, dim3(1), dim3(64 * T), 0, s, d_X, F, tab0, m, p.mscan, us, S,
+                     p.L.NTL, ts0, p.cand, p.best);
+  MW_LAUNCH_CHECK();
+  // step 1's pass takes cur = d(x, c0) itself
+  return kpp_pass_launch(d_X, S, F, d_mu, d_inv, p, 1, nullptr, 0, p.cand, nullptr, T, nullptr, s, true);
 }
 
 int mw_kpp_step(const float* d_X, int64_t S, int F, const double* d_mu, const double* d_inv, int c,

@@ -928,6 +928,7 @@ extern "C" {
 int mw_version(void) { return 10000; }
 const char* mw_last_error(void) { return mw::g_err; }
 int mw_stream_blocks(int64_t n) { return stream_blocks(n); }
+int64_t mw_rows_per_block(int64_t n) { return rows_per_block(n); }
 
 size_t mw_nz_stats_ws_bytes(int64_t n_pix, int C) {
   // worst case over dtypes: the u8 plan has the most blocks

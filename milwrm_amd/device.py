@@ -632,16 +632,18 @@ def mask_rank(mask_u8: torch.Tensor, pending=None):
 
 
 def gather_rows(img_f32: torch.Tensor, feat: torch.Tensor, idx: torch.Tensor, r2p: torch.Tensor,
-                X_out: torch.Tensor, stats: torch.Tensor, accumulate: bool, absmax=None):
+                X_out: torch.Tensor, stats: torch.Tensor, accumulate: bool, absmax=None,
+                keep_records=False):
     """X_out[j] = img[r2p[idx[j]], feat] (``r2p`` None: idx holds the pixels,
     rank_to_pixel); Chan-merge column stats into ``stats`` = [n, mean[F],
     M2[F]] (fp64); max |x| per column maxed into ``absmax`` (fp32 [F],
-    optional)."""
+    optional).  ``keep_records``: the per-block records go to a buffer of
+    their own, returned as a moment segment's (rows_per_block, records)."""
     H, W, C = img_f32.shape
     S, F = X_out.shape
     if S == 0:
-        return
-    ws = WS.get("gather", N.query("mw_gather_ws_bytes", S, F))
+        return None
+    ws = _records_ws(S, F, keep_records, X_out.device)
     with profiling.timed("gather", S * (F * 4 * 2 + 8)):
         if r2p is None:
             N.call("mw_gather_rows_px", P(img_f32), C, P(feat), F, P(idx), S, P(X_out), P(ws), stream())
@@ -654,6 +656,14 @@ def gather_rows(img_f32: torch.Tensor, feat: torch.Tensor, idx: torch.Tensor, r2
     N.call("mw_col_stats_finalize", P(ws), S, F, P(stats), 1 if accumulate else 0, stream())
     if absmax is not None:
         N.call("mw_col_stats_absmax", P(ws), S, F, P(absmax), 1, stream())
+    return (N.query("mw_rows_per_block", S), ws) if keep_records else None
+
+
+def _records_ws(S: int, F: int, keep: bool, dev):
+    """The per-block record buffer of a gather / mw_col_stats_rows: the reused
+    scratch, or (``keep``) a buffer of its own that outlives the call."""
+    nb = N.query("mw_gather_ws_bytes", S, F)
+    return torch.empty(nb, dtype=torch.uint8, device=dev) if keep else WS.get("gather", nb)
 
 
 def rank_to_pixel(idx: torch.Tensor, index: "RankIndex"):
@@ -665,18 +675,21 @@ def rank_to_pixel(idx: torch.Tensor, index: "RankIndex"):
     return idx
 
 
-def col_stats_rows(X: torch.Tensor, stats: torch.Tensor, accumulate: bool, absmax=None):
+def col_stats_rows(X: torch.Tensor, stats: torch.Tensor, accumulate: bool, absmax=None,
+                   keep_records=False):
     """Column statistics of rows already in ``X`` (the records mw_gather_rows
-    would produce for the same rows), Chan-merged into ``stats``."""
+    would produce for the same rows), Chan-merged into ``stats``;
+    ``keep_records`` as gather_rows."""
     S, F = X.shape
     if S == 0:
-        return
-    ws = WS.get("gather", N.query("mw_gather_ws_bytes", S, F))
+        return None
+    ws = _records_ws(S, F, keep_records, X.device)
     with profiling.timed("col_stats", S * F * 4):
         N.call("mw_col_stats_rows", P(X), S, F, P(ws), stream())
     N.call("mw_col_stats_finalize", P(ws), S, F, P(stats), 1 if accumulate else 0, stream())
     if absmax is not None:
         N.call("mw_col_stats_absmax", P(ws), S, F, P(absmax), 1, stream())
+    return (N.query("mw_rows_per_block", S), ws) if keep_records else None
 
 
 # deferred-filter paths taken (blur or median; tests read it); *_streamed: over a slide read band by band (stream.py)

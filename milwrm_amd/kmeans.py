@@ -49,6 +49,24 @@ class DeviceRows:
         # the rows' draws (prep_cluster_data: [(row offset, rows, rank draws,
         # rank base)]): their order in the slides, for spatial_order()
         self.draws = None
+        # the per-block moment records their producer left with the rows
+        # (prep_cluster_data: [(row offset, rows, rows per block, records)], in
+        # row order, covering every row): k-means++ takes step 1's block
+        # potentials from them instead of an init pass (mw_kpp_init_moments).
+        # Only for these rows in this order: whatever reorders, subsets or
+        # shards them builds new DeviceRows, which carry none
+        self.moments = None
+
+    def moment_segments(self):
+        """``moments`` as (count, mw_kpp_seg array), or None when there are
+        none or the entry point does not take them (over 16 segments)."""
+        m = self.moments
+        if not m or len(m) > 16 or sum(n for _, n, _, _ in m) != self.S:
+            return None
+        arr = (N.KppSeg * len(m))()
+        for i, (off, n, rpb, rec) in enumerate(m):
+            arr[i] = N.KppSeg(int(off), int(n), int(rpb), D.P(rec))
+        return len(m), arr
 
     def spatial_order(self):
         """The permutation that puts the rows in slide (pixel) order, or None
@@ -185,17 +203,32 @@ class StandardScaler:
 
 # ----------------------------------------------------------------- k-means
 
-def _kmeans_plusplus_device(rows: DeviceRows, k: int, random_state, n_local_trials=None):
+# k-means++ seedings by how they began: "moments" = step 1 from the rows'
+# moment records (mw_kpp_init_moments), "pass" = the init pass (tests)
+KPP_INIT_USED = {"moments": 0, "pass": 0}
+
+
+def _kmeans_plusplus_device(rows: DeviceRows, k: int, random_state, n_local_trials=None, moments=False):
     S, F = rows.S, rows.F
     T = 2 + int(np.log(k)) if n_local_trials is None else int(n_local_trials)
     u0, steps = kpp_draws(random_state, k, T)
     first = first_center_index(S, u0)
     ws = D.WS.get("kpp", N.query("mw_kpp_ws_bytes", S, T))
     st = D.stream()
-    with profiling.timed("kpp_init", S * (F * 4 + 8)):
-        N.call("mw_kpp_init", D.P(rows.X), S, F, D.P(rows.mu64), D.P(rows.inv64),
-               D.P(rows.X) + int(first) * F * 4, T, D.P(ws), st)
-    for c in range(1, k):
+    segs = rows.moment_segments() if moments and k >= 2 else None
+    if segs is not None:
+        u = np.ascontiguousarray(steps[0], dtype=np.float64)
+        with profiling.timed("kpp_step", S * (F * 4 + 8 * T)):
+            N.call("mw_kpp_init_moments", D.P(rows.X), S, F, D.P(rows.mu64), D.P(rows.inv64),
+                   D.P(rows.X) + int(first) * F * 4, u.ctypes.data, T, segs[0], C.addressof(segs[1]),
+                   D.P(ws), st)
+        KPP_INIT_USED["moments"] += 1
+    else:
+        with profiling.timed("kpp_init", S * (F * 4 + 8)):
+            N.call("mw_kpp_init", D.P(rows.X), S, F, D.P(rows.mu64), D.P(rows.inv64),
+                   D.P(rows.X) + int(first) * F * 4, T, D.P(ws), st)
+        KPP_INIT_USED["pass"] += 1
+    for c in range(1 if segs is None else 2, k):
         u = np.ascontiguousarray(steps[c - 1], dtype=np.float64)
         with profiling.timed("kpp_step", S * (F * 4 + 8 + 8 * T)):
             N.call("mw_kpp_step", D.P(rows.X), S, F, D.P(rows.mu64), D.P(rows.inv64), c,
@@ -913,7 +946,7 @@ class KMeans:
                 seeded = n_init == 1 and isinstance(self.random_state, (int, np.integer)) \
                     and not isinstance(self.random_state, bool)
                 centers0, self.init_indices_ = self._kpp(rows, self.random_state if seeded else rs(),
-                                                         comm)
+                                                         comm, moments=True)
             elif init == "random":
                 if comm.sharded():
                     raise NotImplementedError("init='random' with sharded rows")
@@ -959,24 +992,34 @@ class KMeans:
         # fit returns with that pass queued, so whatever the caller queues next
         # (the label pass) follows it without a host round trip (_Inertia)
         rec = torch.empty(N.query("mw_lloyd_rec_len", k, F), dtype=torch.float64, pin_memory=True)
+        # a k-means++ seeding of rows that carry their moment records starts
+        # from them (mw_kpp_init_moments) instead of the init pass
+        segs = rows.moment_segments() if c0 is None and k >= 2 else None
         with profiling.timed("kmeans_fit", 0):
-            N.call("mw_kmeans_fit_async", D.P(rows.X), S, F, mu.ctypes.data, inv.ctypes.data,
+            N.call("mw_kmeans_fit_async_moments", D.P(rows.X), S, F, mu.ctypes.data, inv.ctypes.data,
                    None if var is None else var.ctypes.data,
                    None if xmax is None else xmax.ctypes.data, k,
                    None if c0 is None else c0.ctypes.data,
                    0 if c0 is not None else int(self.random_state),  # unused with an array init
                    int(self.max_iter), float(self.tol or 0.0), D.P(labels), centers.ctypes.data,
                    C.addressof(n_iter), idx.ctypes.data, D.P(ws), ws.numel(), rec.data_ptr(),
-                   C.addressof(iexp), D.stream())
+                   C.addressof(iexp), 0 if segs is None else segs[0],
+                   None if segs is None else C.addressof(segs[1]), D.stream())
             done = torch.cuda.Event()
             done.record()
+        if c0 is None:
+            KPP_INIT_USED["moments" if segs is not None else "pass"] += 1
         self.init_indices_ = None if c0 is not None else idx
         return labels, _Inertia(done, rec, iexp.value), centers, n_iter.value
 
-    def _kpp(self, rows, rs, comm):
+    def _kpp(self, rows, rs, comm, moments=False):
+        """``moments``: the rows' moment records may stand in for the init
+        pass (``fit`` on the rows as they are; not fit_many, whose fits run
+        over sorted copies or subsets)."""
         if comm.sharded():
+            KPP_INIT_USED["pass"] += 1
             return comm.kpp(rows, int(self.n_clusters), rs)
-        return _kmeans_plusplus_device(rows, int(self.n_clusters), rs)
+        return _kmeans_plusplus_device(rows, int(self.n_clusters), rs, moments=moments)
 
     def _set_fitted(self, rows, labels, inertia, centers, n_iter):
         self._labels_dev = labels
