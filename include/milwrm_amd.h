@@ -15,6 +15,8 @@
  *   mw_lognorm         img.log_normalize                  MxIF.py:416-455
  *   mw_blur            img.blurring('gaussian') → skimage.filters.gaussian →
  *                      scipy.ndimage.gaussian_filter       MxIF.py:375-394
+ *   mw_clahe           img.equalize_hist → skimage equalize_adapthist
+ *                                                          MxIF.py:95-122, 360-373
  *   mw_block_mean      img.downsample → skimage block_reduce MxIF.py:494-517
  *   mw_mask_rank,
  *   mw_gather_rows     img.subsample_pixels (mask gather + fancy index)
@@ -96,6 +98,36 @@ int mw_quantiles(const void* d_img, int dtype, int64_t n_pix, int C,
  * contraction and rounded once to fp32.  NaN stays NaN in modes 0-2. */
 int mw_rescale(const void* d_img, int dtype, int64_t n_pix, int C,
                const double* d_params, float* d_out, void* stream);
+
+/* ---- img.equalize_hist(kernel_size=k) / CLAHE (MxIF.py:95-122, 360-373) ------
+ * Contrast-limited adaptive histogram equalisation of every enabled plane of
+ * an HWC image, fp32 out; the definition (the published equalize_adapthist
+ * procedure restated, G = 16384 grey levels) is DESIGN.md §21.  Per plane:
+ * the minimum and maximum; bins b = rint((a - lo) / (hi - lo) (G - 1)) //
+ * (1 + G / nbins) in fp64; the histogram of every kh x kw tile (tile (i, j)
+ * starts at pixel (i kh, j kw); coordinates past the image are reflected
+ * without repeating the edge); each histogram clipped at
+ * int(max(clip_limit kh kw, 1)) with the excess redistributed (integers
+ * only), summed and scaled into a look-up table of nbins int32 in [0, G - 1];
+ * every pixel the bilinear blend of the tables of the four nearest tile
+ * centres (fp64 weights, fp32 terms summed in a fixed order); the plane
+ * finally rescaled by its own minimum and maximum, (res - rmin) / (rmax -
+ * rmin) in fp64 rounded once.  A constant plane, or one whose blend is
+ * constant, becomes 0.  NaN input is undefined.  Nothing returns to the host
+ * between the stages.
+ * h_enable (host, C ints, or NULL for every plane): planes with 0 are written
+ * as the fp32 conversion of their values.  d_luts_out (device, may be NULL):
+ * the tables, [C][nby][nbx][nbins] int32 with nby = ceil(H / kh), nbx =
+ * ceil(W / kw); zeros for planes that are not enabled or constant.
+ * d_img, d_out and d_ws must be 16-byte aligned; d_out must not alias d_img.
+ * MW_EINVAL: H or W < 2, C < 1, kh outside [1, H], kw outside [1, W],
+ * clip_limit not finite or not positive, nbins < 2, a bad dtype, a null or
+ * misaligned pointer.  MW_EUNSUPPORTED: nbins > 256, C > 256, W * C or
+ * kh * kw of 2^31 or more.  All of them are found before any device call. */
+size_t mw_clahe_ws_bytes(int H, int W, int C, int kh, int kw, int nbins);
+int mw_clahe(const void* d_img, int dtype, int H, int W, int C, const int* h_enable,
+             int kh, int kw, double clip_limit, int nbins, float* d_out,
+             void* d_ws, int* d_luts_out, void* stream);
 
 /* ---- img.blurring('median', size=k) (MxIF.py:395-405 as intended) -----------
  * Median filter per channel over a size_y x size_x window (rows y - size_y/2

@@ -26,13 +26,17 @@ def checktype(obj):
 
 def _out_of_scope(name):
     def f(*a, **k):
-        raise NotImplementedError(f"{name} is outside the MI355X hot path (plotting / adaptive histogram "
-                                  "equalisation); use the reference implementation")
+        raise NotImplementedError(f"{name} is outside the MI355X hot path (plotting); use the reference "
+                                  "implementation")
     f.__name__ = name
     return f
 
 
-CLAHE = _out_of_scope("CLAHE")
+def _need_kernel_size(name):
+    """The message of CLAHE / img.equalize_hist called without kernel_size=."""
+    return NotImplementedError(f"{name}: pass kernel_size= (an int, a (rows, cols) pair, or None for an eighth "
+                               "of the image per axis) to run the device adaptive histogram equalisation")
+
 
 _CLIP_Q = (0.5, 99.5)  # clip_values' percentiles (MxIF.py:47,57)
 
@@ -58,11 +62,11 @@ def _clip_params(vmin, vmax):
     return (vmin, vmax, omin, 1.0, mode)
 
 
-def _module_call(image, op, channels):
-    """clip_values / scale_rgb of a host array through a temporary ``img``."""
+def _module_call(image, op, channels, **kwargs):
+    """clip_values / scale_rgb / CLAHE of a host array through a temporary ``img``."""
     a = np.asarray(image)
     im = img(a)
-    getattr(im, op)(channels=channels)
+    getattr(im, op)(channels=channels, **kwargs)
     out = im._dev.cpu().numpy()
     return out if a.ndim > 2 else out[:, :, 0]
 
@@ -78,6 +82,14 @@ def clip_values(image, channels=None):
 def scale_rgb(image, channels=None):
     """MxIF.py:67-92 on the device (``img.scale``); float64."""
     return _module_call(image, "scale", channels).astype(np.float64)
+
+
+def CLAHE(image=None, channels=None, **kwargs):
+    """MxIF.py:95-122 on the device (``img.equalize_hist``); float64, as the
+    reference's float64 copy.  Only a call that passes ``kernel_size=`` runs."""
+    if "kernel_size" not in kwargs:
+        raise _need_kernel_size("CLAHE")
+    return _module_call(image, "equalize_hist", channels, **kwargs).astype(np.float64)
 
 
 class _DeviceMask:
@@ -534,6 +546,23 @@ class img:
             np.savez_compressed(file, img=self.img, ch=self.ch, mask=self.mask)
 
     # ----------------------------------------------------------- intensity
+    def _channel_rounds(self, channels):
+        """``channels`` of clip / scale / equalize_hist as rounds of distinct
+        plane indices: [None] (every plane at once) for None or a 2-D image;
+        a channel listed twice is in two rounds."""
+        if channels is None or self._ndim == 2:
+            return [None]
+        if isinstance(channels, (int, np.integer, str)):
+            channels = (channels,)
+        todo = self._features(list(channels))
+        rounds = []
+        while todo:
+            uniq = list(dict.fromkeys(todo))
+            rounds.append(uniq)
+            for c in uniq:
+                todo.remove(c)
+        return rounds
+
     def _intensity(self, channels, select, rows_of):
         """clip / scale: pending transforms applied, then per round one exact
         selection (D.quantiles, one host read of its few numbers) and one
@@ -546,19 +575,7 @@ class img:
                                       "whole slide's")
         t = self._materialize()  # a slide that is not resident: _device()'s MemoryError
         C = int(t.shape[2])
-        if channels is None or self._ndim == 2:
-            rounds = [None]
-        else:
-            if isinstance(channels, (int, np.integer, str)):
-                channels = (channels,)
-            todo = self._features(list(channels))
-            rounds = []
-            while todo:
-                uniq = list(dict.fromkeys(todo))
-                rounds.append(uniq)
-                for c in uniq:
-                    todo.remove(c)
-        for chs in rounds:
+        for chs in self._channel_rounds(channels):
             params = np.zeros((C, 5), dtype=np.float64)  # mode 0: the value itself
             if chs is None:
                 params[:] = rows_of(D.d2h(select(t, True))[0])
@@ -598,7 +615,35 @@ class img:
 
         self._intensity(channels, lambda t, pooled: D.quantiles(t, (0.0, 100.0), pooled=pooled), rows_of)
 
-    equalize_hist = _out_of_scope("img.equalize_hist")
+    def equalize_hist(self=None, channels=None, **kwargs):
+        """MxIF.py:360-373 / CLAHE (MxIF.py:95-122): contrast-limited adaptive
+        histogram equalisation per plane (D.clahe; the definition, and how it
+        relates to skimage's equalize_adapthist: DESIGN.md §21).  Only a call
+        that passes ``kernel_size=`` runs: an int, a (rows, cols) pair, or
+        None for an eighth of the image per axis; ``clip_limit`` (0.01) and
+        ``nbins`` (256, at most 256) as skimage's.  ``channels`` as ``clip``:
+        None (or a 2-D image) means every plane, else indices or names, the
+        other planes unchanged; a plane listed twice is equalised twice.  The
+        pixels become fp32."""
+        if "kernel_size" not in kwargs:  # also for the unbound call with no arguments at all
+            raise _need_kernel_size("img.equalize_hist")
+        kernel_size = kwargs.pop("kernel_size")
+        clip_limit = kwargs.pop("clip_limit", 0.01)
+        nbins = kwargs.pop("nbins", 256)
+        if kwargs:
+            raise NotImplementedError(f"equalize_hist options {kwargs} (kernel_size, clip_limit and nbins are "
+                                      "implemented)")
+        if getattr(self, "_band", None) is not None:
+            raise NotImplementedError("equalize_hist of a row band of a slide: the tiles and the extremes are the "
+                                      "whole slide's")
+        D.clahe_args(self.shape[0], self.shape[1], kernel_size, clip_limit, nbins)  # before any device call
+        t = self._materialize()  # a slide that is not resident: _device()'s MemoryError
+        for chs in self._channel_rounds(channels):
+            t = D.clahe(t, kernel_size, clip_limit, nbins, enable=chs)
+        self._set_device(t)
+        self._xbound = None
+        self._lognorm_host = None
+
     show = _out_of_scope("img.show")
     plot_image_histogram = _out_of_scope("img.plot_image_histogram")
 

@@ -40,6 +40,9 @@ _PROTOS = {
     "mw_quantiles_ws_bytes": (c_sz, [c_i32, c_i32]),
     "mw_quantiles": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mw_rescale": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "mw_clahe_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "mw_clahe": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, C.c_double, c_i32, c_vp, c_vp, c_vp,
+                         c_vp]),
     "mw_median_is_network": (c_i32, [c_i32, c_i32]),
     "mw_median": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     "mw_median_generic": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),

@@ -319,6 +319,80 @@ def rescale(img: torch.Tensor, params, out=None) -> torch.Tensor:
     return out
 
 
+CLAHE_MAX_BINS = 256
+
+
+def clahe_args(H, W, kernel_size, clip_limit=0.01, nbins=256):
+    """The arguments of CLAHE checked on the host (no device call): (kh, kw,
+    clip_limit, nbins).  ``kernel_size``: an int k for (k, k), a (rows, cols)
+    pair, or None for (max(H // 8, 1), max(W // 8, 1)).  ValueError: a pair of
+    another length, kh or kw below 1 or above the image's extent, H or W below
+    2, clip_limit not finite or not positive, nbins below 2;
+    NotImplementedError: nbins above 256."""
+    def whole(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"CLAHE {name} must be an int, got {v!r}")
+        return int(v)
+
+    H, W = int(H), int(W)
+    if H < 2 or W < 2:
+        raise ValueError(f"CLAHE needs an image of at least 2 x 2 pixels, got {H} x {W}")
+    if kernel_size is None:
+        kh, kw = max(H // 8, 1), max(W // 8, 1)
+    elif isinstance(kernel_size, (tuple, list, np.ndarray)):
+        if len(kernel_size) != 2:
+            raise ValueError(f"CLAHE kernel_size must be an int, a (rows, cols) pair or None, got {kernel_size!r}")
+        kh, kw = whole(kernel_size[0], "kernel_size"), whole(kernel_size[1], "kernel_size")
+    else:
+        kh = kw = whole(kernel_size, "kernel_size")
+    if kh < 1 or kw < 1:
+        raise ValueError(f"CLAHE kernel_size must be at least 1, got {kernel_size!r}")
+    if kh > H or kw > W:
+        raise ValueError(f"CLAHE kernel_size {(kh, kw)} exceeds the image's extent {(H, W)}")
+    if isinstance(clip_limit, (bool, str)) or not isinstance(clip_limit, (int, float, np.integer, np.floating)):
+        raise ValueError(f"CLAHE clip_limit must be a positive finite number, got {clip_limit!r}")
+    clip_limit = float(clip_limit)
+    if not (np.isfinite(clip_limit) and clip_limit > 0):
+        raise ValueError(f"CLAHE clip_limit must be a positive finite number, got {clip_limit!r}")
+    nbins = whole(nbins, "nbins")
+    if nbins < 2:
+        raise ValueError(f"CLAHE nbins must be at least 2, got {nbins}")
+    if nbins > CLAHE_MAX_BINS:
+        raise NotImplementedError(f"CLAHE nbins {nbins} (up to {CLAHE_MAX_BINS})")
+    return kh, kw, clip_limit, nbins
+
+
+def clahe(img: torch.Tensor, kernel_size, clip_limit=0.01, nbins=256, enable=None, out=None, luts: bool = False):
+    """Contrast-limited adaptive histogram equalisation of an HWC image per
+    plane (mw_clahe; the definition: DESIGN.md §21), fp32 out.  ``enable``: the
+    planes to equalise (indices; None: all of them), the others come back as
+    the fp32 conversion of their values.  ``luts``: also return the look-up
+    tables, int32 [C, nby, nbx, nbins].  Arguments are checked on the host
+    first (``clahe_args``); nothing is synchronised."""
+    H, W, C = img.shape
+    kh, kw, clip_limit, nbins = clahe_args(H, W, kernel_size, clip_limit, nbins)
+    if not img.is_contiguous():
+        raise ValueError("clahe: the image must be contiguous")
+    if out is None:
+        out = torch.empty((H, W, C), dtype=torch.float32, device=img.device)
+    elif out.dtype != torch.float32 or out.shape != img.shape or not out.is_contiguous():
+        raise ValueError(f"clahe: out must be a contiguous float32 tensor of shape {tuple(img.shape)}")
+    if out.data_ptr() == img.data_ptr():
+        raise ValueError("clahe: the output must not alias the image")
+    en = None
+    if enable is not None:
+        en = np.zeros(C, dtype=np.int32)
+        en[np.asarray(list(enable), dtype=np.int64)] = 1
+    nby, nbx = -(-H // kh), -(-W // kw)
+    lut = torch.empty((C, nby, nbx, nbins), dtype=torch.int32, device=img.device) if luts else None
+    ws = WS.get("clahe", N.query("mw_clahe_ws_bytes", H, W, C, kh, kw, nbins))
+    # the image read three times (range, histograms, map), the output written once and rescaled in place
+    with profiling.timed("clahe", H * W * C * (3 * img.element_size() + 12)):
+        N.call("mw_clahe", P(img), dtype_code(img), H, W, C, None if en is None else en.ctypes.data, kh, kw,
+               clip_limit, nbins, P(out), P(ws), P(lut), stream())
+    return (out, lut) if luts else out
+
+
 def gaussian_taps(sigma: float, truncate: float = 4.0) -> np.ndarray:
     """scipy ``_gaussian_kernel1d`` order 0 (radius int(truncate*sigma+0.5)),
     computed in fp64 then rounded to fp32 for the kernel."""
