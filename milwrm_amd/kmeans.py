@@ -791,7 +791,7 @@ def fit_many(rows: DeviceRows, k_values, random_state=None, comm=None, **kw):
     models = []
     for k in k_values:
         km = KMeans(n_clusters=int(k), random_state=random_state, **kw)
-        km._check(rows.S)
+        km._check(rows.S, rows.F)
         if km.n_init not in ("auto", 1) or not isinstance(km.init, str) or km.init != "k-means++":
             raise NotImplementedError("fit_many: k-means++ with a single init only")
         km._tol = float(np.mean(rows.feature_var()) * km.tol) if km.tol else 0.0
@@ -889,7 +889,7 @@ class KMeans:
             setattr(self, k, v)
         return self
 
-    def _check(self, S):
+    def _check(self, S, F):
         if not isinstance(self.n_clusters, (int, np.integer)) or self.n_clusters < 1:
             raise ValueError(f"n_clusters must be a positive int, got {self.n_clusters!r}")
         if S < self.n_clusters:
@@ -898,13 +898,15 @@ class KMeans:
             raise NotImplementedError("only algorithm='lloyd' is implemented on the device")
         if self.n_clusters > 64:
             raise NotImplementedError("n_clusters > 64 is not supported by the device kernels")
+        if F > 64:
+            raise NotImplementedError(f"{F} features: more than 64 are not supported by the device kernels")
 
     def fit(self, X, y=None, sample_weight=None, comm=None):
         comm = LOCAL if comm is None else comm
         if sample_weight is not None and not np.all(np.asarray(sample_weight) == 1):
             raise NotImplementedError("non-unit sample_weight")
         rows = X if isinstance(X, DeviceRows) else DeviceRows.from_host(X)
-        self._check(rows.S)
+        self._check(rows.S, rows.F)
         k = int(self.n_clusters)
         self._tol = float(np.mean(rows.feature_var()) * self.tol) if self.tol else 0.0
         init = self.init
