@@ -607,6 +607,39 @@ int mw_kmeans_fit_async_moments(const float* d_X, int64_t S, int F, const double
                                 uint8_t* d_labels, double* h_centers, int* h_n_iter, int64_t* h_init_idx,
                                 void* d_ws, size_t ws_bytes, double* h_final_rec, int* h_inertia_exp,
                                 int n_seg, const mw_kpp_seg* h_segs, void* stream);
+/* mw_kmeans_fit_async_moments without the final pass: everything up to and
+ * including the last Lloyd iteration.  h_centers, *h_n_iter and h_init_idx
+ * are final at return and *h_strict says whether the fit converged strictly
+ * (no label changed in its last iteration); `stream` is synchronised.
+ * d_labels then holds the LAST ITERATION's labels: sklearn's labels_ only when
+ * *h_strict is 1.  The labels under the final centers and the inertia are
+ * mw_kmeans_fit_finish's, whenever (and if) the caller wants them; a caller
+ * that needs only the centers (the label pass over the slides) never pays
+ * that pass over the rows.  mw_kmeans_fit_history lists what the fit read: no
+ * final-pass entry. */
+int mw_kmeans_fit_deferred(const float* d_X, int64_t S, int F, const double* h_mu,
+                           const double* h_inv, const double* h_feature_var, const float* h_xmax,
+                           int k, const double* h_init, uint32_t seed, int max_iter, double tol,
+                           uint8_t* d_labels, double* h_centers, int* h_n_iter, int64_t* h_init_idx,
+                           void* d_ws, size_t ws_bytes, int n_seg, const mw_kpp_seg* h_segs,
+                           int* h_strict, void* stream);
+/* The final pass of a fit that mw_kmeans_fit_deferred left out, over the same
+ * rows, scaler and column maxima (h_xmax[F], required) with the fit's
+ * h_centers, strict flag and d_labels: the extra E-step (strict = 0; d_labels
+ * rewritten) or none (strict = 1), and the inertia.  Bit for bit the labels
+ * and inertia of the eager entries.  The pass is queued on `stream` and its
+ * record copied to the caller's PAGE-LOCKED h_final_rec as by
+ * mw_kmeans_fit_async (inertia = (rec[rl - 2] * 2^32 + rec[rl - 1]) *
+ * 2^-(*h_inertia_exp) once the stream got there).  d_ws:
+ * mw_kmeans_fit_finish_ws_bytes(S, F, k) bytes of its own (required; nothing
+ * of the fit's workspace is read).  The fit history is left alone.
+ * MW_EINVAL before any launch: a null pointer, k or F outside [1, 64], S < k,
+ * a short workspace. */
+size_t mw_kmeans_fit_finish_ws_bytes(int64_t S, int F, int k);
+int mw_kmeans_fit_finish(const float* d_X, int64_t S, int F, const double* h_mu, const double* h_inv,
+                         const float* h_xmax, int k, const double* h_centers, int strict,
+                         uint8_t* d_labels, void* d_ws, size_t ws_bytes, double* h_final_rec,
+                         int* h_inertia_exp, void* stream);
 
 /* ---- batched fits: the find_optimal_k sweep's Lloyd iterations ----------------
  * Replaces kMeansRes' per-k `KMeans(n_clusters=k, random_state=seed).fit(X)`

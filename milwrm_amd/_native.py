@@ -106,6 +106,11 @@ _PROTOS = {
     "mw_kmeans_fit_async_moments": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_u32, c_i32,
                                             C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_i32,
                                             c_vp, c_vp]),
+    "mw_kmeans_fit_deferred": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_u32, c_i32,
+                                       C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_i32, c_vp, c_vp, c_vp]),
+    "mw_kmeans_fit_finish_ws_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "mw_kmeans_fit_finish": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_sz,
+                                     c_vp, c_vp, c_vp]),
     "mw_lloyd_fits": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, C.c_double,
                               c_i32, c_i32, C.c_double, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,

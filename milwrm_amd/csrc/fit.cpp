@@ -11,7 +11,9 @@
 //   * Lloyd: mw_lloyd_pass per iteration (exact fixed-point sums), strict
 //     convergence on zero changed labels, else the center-shift test;
 //     empty-cluster relocation and averaging   (_k_means_common.pyx:181-311)
-//   * the extra E-step when not strictly converged, and the inertia.
+//   * the extra E-step when not strictly converged, and the inertia
+//     (fit_tail; mw_kmeans_fit_deferred leaves this pass to a later
+//     mw_kmeans_fit_finish, for callers that may never read its outputs).
 // numpy's reductions used by the Python side (pairwise sums) are restated
 // (np_sum) so the host arithmetic matches it bit for bit.
 #include <hip/hip_runtime.h>
@@ -30,6 +32,9 @@
 namespace mw {
 void mt_init_genrand(uint32_t seed, uint32_t* mt);
 void mt_regen(uint32_t* mt);
+// kpp.hip: mw_kpp_step with the choice of not storing cur (the last step)
+int kpp_step(const float* d_X, int64_t S, int F, const double* d_mu, const double* d_inv, int c,
+             const double* h_u, int T, void* d_ws, void* stream, bool store_cur);
 
 namespace {
 
@@ -395,6 +400,69 @@ static FitLayout fit_layout(int64_t S, int F, int k) {
   return L;
 }
 
+// Workspace of mw_kmeans_fit_finish: a32[64] b32[64] qexp[64] | par | the
+// pass's per-block records | its record.  Modes 1 and 2 read no bounds.
+struct FinishLayout {
+  size_t small, par, lws, out, total;
+};
+static FinishLayout finish_layout(int64_t S, int F, int k) {
+  FinishLayout L;
+  L.small = 0;
+  L.par = fal(64 * 4 * 3);
+  L.lws = L.par + fal(((size_t)k * F + 2 * k) * 4);
+  L.out = L.lws + fal(mw_lloyd_ws_bytes_kinds(S, k, F, 0));
+  L.total = L.out + fal((size_t)mw_lloyd_rec_len(k, F) * 8);
+  return L;
+}
+
+// The end of a fit from its final centers (fit.a64 / b64 and the device
+// scaler set): the inertia's fixed-point exponent from a bound on any row's
+// squared distance, the center table, the final pass (mode 1: the extra E-step
+// and inertia; mode 2, strictly converged: inertia of the labels as they are)
+// and the inertia from its record.  async_end: the pass and its record's copy
+// into the caller's page-locked h_final_rec are queued; the caller reads the
+// inertia, (rec[rl - 2] * 2^32 + rec[rl - 1]) * 2^-iexp, after the stream
+// reaches them (the labels likewise: stream-ordered).  The staging the table
+// came from stays busy until then.
+static int fit_tail(Fit& fit, const float* xmax, const std::vector<double>& centers, bool strict,
+                    bool async_end, double* h_inertia, double* h_final_rec, int* h_inertia_exp) {
+  const int F = fit.F, k = fit.k;
+  std::vector<double> xs2(F), tmp(std::max(F, k));
+  for (int f = 0; f < F; ++f) {
+    const double v = std::fabs(fit.a64[f]) * (double)xmax[f] + std::fabs(fit.b64[f]);
+    xs2[f] = v * v;
+  }
+  const double xnorm = std::sqrt(np_sum(xs2.data(), F));
+  double cmax = 0.0;
+  for (int j = 0; j < k; ++j) {
+    for (int f = 0; f < F; ++f) tmp[f] = centers[(size_t)j * F + f] * centers[(size_t)j * F + f];
+    const double v = std::sqrt(np_sum(tmp.data(), F));
+    cmax = j == 0 ? v : std::max(cmax, v);
+  }
+  const double xc = xnorm + cmax;
+  const int iexp = exp_below(xc * xc * 1.01);
+  MW_TRY(fit.upload(centers));
+  if (async_end && h_final_rec && pinned_staging()) {
+    MW_TRY(fit.pass_async(strict ? 2 : 1, 0, iexp, h_final_rec));
+    *h_inertia_exp = iexp;
+    hipEvent_t ev;
+    MW_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    MW_HIP(hipEventRecord(ev, fit.st));
+    pin_busy = ev;
+    *h_inertia = std::numeric_limits<double>::quiet_NaN();
+    return MW_OK;
+  }
+  std::vector<double> rec;
+  MW_TRY(fit.pass(strict ? 2 : 1, 0, iexp, rec));
+  const double* tail = rec.data() + fit.rl - 4;
+  *h_inertia = (tail[2] * 4294967296.0 + tail[3]) * std::ldexp(1.0, -iexp);
+  if (h_final_rec) {
+    std::memcpy(h_final_rec, rec.data(), (size_t)fit.rl * sizeof(double));
+    *h_inertia_exp = iexp;
+  }
+  return MW_OK;
+}
+
 }  // namespace
 }  // namespace mw
 
@@ -410,7 +478,7 @@ static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_m
                            uint32_t seed, int max_iter, double tol, uint8_t* d_labels, double* h_centers,
                            double* h_inertia, int* h_n_iter, int64_t* h_init_idx, void* d_ws, size_t ws_bytes,
                            double* h_final_rec, int* h_inertia_exp, void* stream, int n_seg = 0,
-                           const mw_kpp_seg* h_segs = nullptr);
+                           const mw_kpp_seg* h_segs = nullptr, int* h_strict = nullptr);
 
 // per pass of the thread's last single fit: kind, changed, recomputed, rows read
 static thread_local std::vector<int64_t> fit_hist;
@@ -460,12 +528,84 @@ extern "C" int mw_kmeans_fit_async_moments(const float* d_X, int64_t S, int F, c
                          h_inertia_exp, stream, n_seg, h_segs);
 }
 
+extern "C" int mw_kmeans_fit_deferred(const float* d_X, int64_t S, int F, const double* h_mu,
+                                      const double* h_inv, const double* h_feature_var, const float* h_xmax,
+                                      int k, const double* h_init, uint32_t seed, int max_iter, double tol,
+                                      uint8_t* d_labels, double* h_centers, int* h_n_iter,
+                                      int64_t* h_init_idx, void* d_ws, size_t ws_bytes, int n_seg,
+                                      const mw_kpp_seg* h_segs, int* h_strict, void* stream) {
+  MW_CHECK_ARG(h_strict, "mw_kmeans_fit_deferred: null h_strict");
+  MW_CHECK_ARG(n_seg == 0 || h_segs, "mw_kmeans_fit_deferred: null segments");
+  double unused = 0.0;
+  return kmeans_fit_impl(d_X, S, F, h_mu, h_inv, h_feature_var, h_xmax, k, h_init, seed, max_iter, tol,
+                         d_labels, h_centers, &unused, h_n_iter, h_init_idx, d_ws, ws_bytes, nullptr, nullptr,
+                         stream, n_seg, h_segs, h_strict);
+}
+
+extern "C" size_t mw_kmeans_fit_finish_ws_bytes(int64_t S, int F, int k) {
+  if (S <= 0 || F < 1 || F > 64 || k < 1 || k > 64) return 0;
+  return finish_layout(S, F, k).total;
+}
+
+extern "C" int mw_kmeans_fit_finish(const float* d_X, int64_t S, int F, const double* h_mu,
+                                    const double* h_inv, const float* h_xmax, int k, const double* h_centers,
+                                    int strict, uint8_t* d_labels, void* d_ws, size_t ws_bytes,
+                                    double* h_final_rec, int* h_inertia_exp, void* stream) {
+  MW_CHECK_ARG(d_X && h_mu && h_inv && h_xmax && h_centers && d_labels && d_ws && h_final_rec && h_inertia_exp,
+               "mw_kmeans_fit_finish: null pointer");
+  MW_CHECK_ARG(F >= 1 && F <= 64, "mw_kmeans_fit_finish: F=%d outside [1, 64]", F);
+  MW_CHECK_ARG(k >= 1 && k <= 64, "mw_kmeans_fit_finish: n_clusters=%d outside [1, 64]", k);
+  MW_CHECK_ARG(S >= k, "mw_kmeans_fit_finish: n_samples=%lld should be >= n_clusters=%d", (long long)S, k);
+  const FinishLayout L = finish_layout(S, F, k);
+  MW_CHECK_ARG(ws_bytes >= L.total, "mw_kmeans_fit_finish: workspace %zu < %zu bytes", ws_bytes, L.total);
+  char* base = static_cast<char*>(d_ws);
+  Fit fit;
+  fit.S = S;
+  fit.F = F;
+  fit.k = k;
+  fit.st = as_stream(stream);
+  fit.X = d_X;
+  fit.rl = mw_lloyd_rec_len(k, F);
+  fit.a32 = reinterpret_cast<float*>(base + L.small);
+  fit.b32 = fit.a32 + 64;
+  fit.qexp = reinterpret_cast<int32_t*>(fit.b32 + 64);
+  fit.par = reinterpret_cast<float*>(base + L.par);
+  fit.ub = fit.lb = nullptr;  // modes 1 and 2 read no bounds
+  fit.ws = base + L.lws;
+  fit.out = reinterpret_cast<double*>(base + L.out);
+  fit.labels = d_labels;
+  // the folded scaler and the fixed-point exponents, as the fit uploaded them
+  fit.a64.resize(F);
+  fit.b64.resize(F);
+  std::vector<char> blk(64 * 4 * 3, 0);
+  float* fa = reinterpret_cast<float*>(blk.data());
+  int32_t* qi = reinterpret_cast<int32_t*>(fa + 128);
+  for (int f = 0; f < F; ++f) {
+    fa[f] = (float)h_inv[f];
+    fa[64 + f] = (float)(-h_mu[f] * h_inv[f]);
+    qi[f] = exp_below((double)h_xmax[f]);
+    fit.a64[f] = (double)fa[f];
+    fit.b64[f] = (double)fa[64 + f];
+  }
+  char* pin = pinned_staging();
+  const void* src = blk.data();
+  if (pin) {
+    std::memcpy(pin + kPinSetup, blk.data(), blk.size());
+    src = pin + kPinSetup;
+  }
+  MW_HIP(hipMemcpyAsync(fit.a32, src, blk.size(), hipMemcpyHostToDevice, fit.st));
+  if (!pin) MW_HIP(hipStreamSynchronize(fit.st));  // pageable source must outlive the copy
+  const std::vector<double> centers(h_centers, h_centers + (size_t)k * F);
+  double unused = 0.0;
+  return fit_tail(fit, h_xmax, centers, strict != 0, true, &unused, h_final_rec, h_inertia_exp);
+}
+
 static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_mu, const double* h_inv,
                            const double* h_feature_var, const float* h_xmax, int k, const double* h_init,
                            uint32_t seed, int max_iter, double tol, uint8_t* d_labels, double* h_centers,
                            double* h_inertia, int* h_n_iter, int64_t* h_init_idx, void* d_ws, size_t ws_bytes,
                            double* h_final_rec, int* h_inertia_exp, void* stream, int n_seg,
-                           const mw_kpp_seg* h_segs) {
+                           const mw_kpp_seg* h_segs, int* h_strict) {
   MW_CHECK_ARG(d_X && h_mu && h_inv && d_labels && h_centers && h_inertia && h_n_iter,
                "mw_kmeans_fit: null pointer");
   MW_CHECK_ARG(F >= 1 && F <= 64, "mw_kmeans_fit: F=%d outside [1, 64]", F);
@@ -619,8 +759,8 @@ static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_m
         MW_TRY(mw_kpp_step_fold(d_X, S, F, d_mu, d_inv, c, u.data(), T, big, first, fit.a32, fit.b32, fit.qexp,
                                 d_labels, fit.ub, fit.lb, d_moved, base + L.fold, reinterpret_cast<double*>(fit.ws),
                                 fit.out + fit.rl, st));
-      else
-        MW_TRY(mw_kpp_step(d_X, S, F, d_mu, d_inv, c, u.data(), T, big, st));
+      else  // nothing reads cur after the last step: its pass does not store it
+        MW_TRY(kpp_step(d_X, S, F, d_mu, d_inv, c, u.data(), T, big, st, c < k - 1));
     }
     MW_TRY(mw_kpp_indices(big, S, T, k, d_idx, st));
     std::vector<int64_t> idx(k);
@@ -756,48 +896,19 @@ static int kmeans_fit_impl(const float* d_X, int64_t S, int F, const double* h_m
   }
   if (!done) n_iter = max_iter;
 
-  // final pass: extra E-step unless strictly converged, and inertia
-  std::vector<double> xs2(F), cn(k);
-  for (int f = 0; f < F; ++f) {
-    const double v = std::fabs(fit.a64[f]) * (double)xmax[f] + std::fabs(fit.b64[f]);
-    xs2[f] = v * v;
-  }
-  const double xnorm = std::sqrt(np_sum(xs2.data(), F));
-  double cmax = 0.0;
-  for (int j = 0; j < k; ++j) {
-    for (int f = 0; f < F; ++f) tmp[f] = centers[(size_t)j * F + f] * centers[(size_t)j * F + f];
-    const double v = std::sqrt(np_sum(tmp.data(), F));
-    cmax = j == 0 ? v : std::max(cmax, v);
-  }
-  const double xc = xnorm + cmax;
-  const int iexp = exp_below(xc * xc * 1.01);
-  MW_TRY(fit.upload(centers));
-  fit_hist.insert(fit_hist.end(), {(int64_t)(strict ? 12 : 11), -1, -1, S});  // the final pass reads every row
   *h_n_iter = n_iter;
   std::memcpy(h_centers, centers.data(), centers.size() * sizeof(double));
-  if (h_final_rec && !own.p && pinned_staging()) {  // (a workspace allocated here is freed on return: synchronous end)
-    // asynchronous end: the final pass and its record's copy into the caller's
-    // page-locked h_final_rec are queued; the caller reads the inertia,
-    // (rec[rl - 2] * 2^32 + rec[rl - 1]) * 2^-iexp, after `stream` reaches
-    // here (the labels likewise: stream-ordered).  The staging the table came
-    // from stays busy until then.
-    MW_TRY(fit.pass_async(strict ? 2 : 1, 0, iexp, h_final_rec));
-    *h_inertia_exp = iexp;
-    hipEvent_t ev;
-    MW_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    MW_HIP(hipEventRecord(ev, st));
-    pin_busy = ev;
-    *h_inertia = std::numeric_limits<double>::quiet_NaN();
+  if (h_strict) {
+    // deferred end (mw_kmeans_fit_deferred): the centers are final here; the
+    // final pass is mw_kmeans_fit_finish's, queued when its outputs are asked
+    // for.  d_labels holds the last iteration's labels until then.
+    *h_strict = strict ? 1 : 0;
     return MW_OK;
   }
-  MW_TRY(fit.pass(strict ? 2 : 1, 0, iexp, rec));
-  const double* tail = rec.data() + fit.rl - 4;
-  *h_inertia = (tail[2] * 4294967296.0 + tail[3]) * std::ldexp(1.0, -iexp);
-  if (h_final_rec) {
-    std::memcpy(h_final_rec, rec.data(), (size_t)fit.rl * sizeof(double));
-    *h_inertia_exp = iexp;
-  }
-  return MW_OK;
+  // final pass: extra E-step unless strictly converged, and inertia
+  fit_hist.insert(fit_hist.end(), {(int64_t)(strict ? 12 : 11), -1, -1, S});  // the final pass reads every row
+  // (a workspace allocated here is freed on return: synchronous end)
+  return fit_tail(fit, xmax.data(), centers, strict, !own.p, h_inertia, h_final_rec, h_inertia_exp);
 }
 
 // ---------------------------------------------------------------------------

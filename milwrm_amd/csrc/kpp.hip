@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
     const float* __restrict__ X, int64_t S, int F, const double* __restrict__ tab,
     const double* __restrict__ tab_prev, const int* __restrict__ best, int best_val,
     double* __restrict__ cur, int64_t R, int64_t NTL, double* __restrict__ bsum_new,
-    double* __restrict__ tsum_new) {
+    double* __restrict__ tsum_new, int store_cur) {
   constexpr int NV = FMAX / 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* s_red = reinterpret_cast<double*>(smem);  // [4] block-sum scratch
@@ -405,7 +405,9 @@ __global__ void __launch_bounds__(256, FMAX == 64 ? 2 : 4) kpp_pass_kernel(
     if (MODE == 0) cd = d[0];
     if (MODE == 2) cd = cd < dp ? cd : dp;
     if (MODE == 3) cd = dp;
-    if (MODE != 1 && valid) cur[row] = cd;
+    // store_cur = 0 (a launch argument: wave-uniform): the last step of a
+    // seeding, after which nothing reads cur
+    if (MODE != 1 && valid && store_cur) cur[row] = cd;
     double mv[T];
 #pragma unroll
     for (int c = 0; c < T; ++c) {
@@ -1020,7 +1022,7 @@ __global__ void __launch_bounds__(1024) kpp_search_kernel(
 static int kpp_pass_launch(const float* X, int64_t S, int F, const double* mu, const double* inv,
                            const KppPtrs& p, int c, const int* best, int best_val,
                            const int64_t* cand, const float* rows, int T, int64_t* chosen_reset,
-                           hipStream_t s, bool c0_pending = false) {
+                           hipStream_t s, bool c0_pending = false, bool store_cur = true) {
   double* tab = p.tab_of(c);
   hipLaunchKernelGGL(kpp_prep_kernel, dim3(1), dim3(512), 0, s, X, F, mu, inv, cand, rows, T, tab,
                      chosen_reset);
@@ -1034,7 +1036,7 @@ static int kpp_pass_launch(const float* X, int64_t S, int F, const double* mu, c
   const int64_t R = krows(S);
 #define MW_KP(FMV, TV, MV)                                                                      \
   hipLaunchKernelGGL((kpp_pass_kernel<FMV, TV, MV>), dim3(p.L.G), dim3(256), lds, s, X, S, F, tab, \
-                     tab_prev, best, best_val, p.cur, R, p.L.NTL, bs, tsm)
+                     tab_prev, best, best_val, p.cur, R, p.L.NTL, bs, tsm, store_cur ? 1 : 0)
 #define MW_KPM(FMV, TV) \
   if (mode == 1) MW_KP(FMV, TV, 1); else if (mode == 3) MW_KP(FMV, TV, 3); else MW_KP(FMV, TV, 2);
 #define MW_KPT(FMV)                                                                        \
@@ -1066,6 +1068,23 @@ static int kpp_search_launch(const float* X, int64_t S, int F, const KppPtrs& p,
                      u[5], u[6], u[7], n_tgt, p.cand, p.chosen, p.best, best_given, rv_given);
   MW_LAUNCH_CHECK();
   return MW_OK;
+}
+
+// mw_kpp_step (arguments checked there).  store_cur = false, the fit driver's
+// last step only: the pass does not write cur, which nothing reads after the
+// last step (mw_kpp_indices selects from the block sums); the public entry
+// always leaves its state complete.
+int kpp_step(const float* d_X, int64_t S, int F, const double* d_mu, const double* d_inv, int c,
+             const double* h_u, int T, void* d_ws, void* stream, bool store_cur) {
+  const KppPtrs p = kpp_ptrs(d_ws, S, T);
+  double u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < T; ++i) u[i] = h_u[i];
+  hipStream_t s = as_stream(stream);
+  // select the previous step's best (c >= 2), then locate this step's candidates
+  const int rc = kpp_search_launch(d_X, S, F, p, c, c == 1 ? 1 : T, u, T, T, -1, nullptr, s);
+  if (rc != MW_OK) return rc;
+  return kpp_pass_launch(d_X, S, F, d_mu, d_inv, p, c, p.best, 0, p.cand, nullptr, T, nullptr, s, false,
+                         store_cur);
 }
 
 }  // namespace mw
@@ -1155,14 +1174,7 @@ int mw_kpp_step(const float* d_X, int64_t S, int F, const double* d_mu, const do
   MW_CHECK_ARG(d_X && d_mu && d_inv && d_ws && h_u, "mw_kpp_step: null pointer");
   MW_CHECK_ARG(c >= 1 && c < 256, "mw_kpp_step: center index %d out of range", c);
   MW_CHECK_ARG(T >= 1 && T <= 8 && F > 0 && F <= 64, "mw_kpp_step: T in [1,8], F <= 64 required");
-  const KppPtrs p = kpp_ptrs(d_ws, S, T);
-  double u[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < T; ++i) u[i] = h_u[i];
-  hipStream_t s = as_stream(stream);
-  // select the previous step's best (c >= 2), then locate this step's candidates
-  const int rc = kpp_search_launch(d_X, S, F, p, c, c == 1 ? 1 : T, u, T, T, -1, nullptr, s);
-  if (rc != MW_OK) return rc;
-  return kpp_pass_launch(d_X, S, F, d_mu, d_inv, p, c, p.best, 0, p.cand, nullptr, T, nullptr, s);
+  return kpp_step(d_X, S, F, d_mu, d_inv, c, h_u, T, d_ws, stream, true);
 }
 
 int mw_kpp_fold_supported(int k, int F, int T) {

@@ -206,6 +206,8 @@ class StandardScaler:
 # k-means++ seedings by how they began: "moments" = step 1 from the rows'
 # moment records (mw_kpp_init_moments), "pass" = the init pass (tests)
 KPP_INIT_USED = {"moments": 0, "pass": 0}
+# final passes of deferred fits that ran (KMeans._finish; tests)
+FIT_FINISH_USED = {"finish": 0}
 
 
 def _kmeans_plusplus_device(rows: DeviceRows, k: int, random_state, n_local_trials=None, moments=False):
@@ -858,13 +860,29 @@ class _Inertia:
         return float((r[-2] * 4294967296.0 + r[-1]) * 2.0 ** -self.iexp)
 
 
+class _Deferred:
+    """What the final pass of a fit through mw_kmeans_fit_deferred needs when
+    it is run later (mw_kmeans_fit_finish): the rows (a strong reference: they
+    live as long as the model, or until the pass has run), their scaler and
+    column maxima, the final centers, and whether the fit converged strictly."""
+
+    def __init__(self, X: torch.Tensor, mu, inv, xmax, strict: bool, centers):
+        self.X, self.mu, self.inv, self.xmax, self.strict = X, mu, inv, xmax, bool(strict)
+        self.centers = np.array(centers, dtype=np.float64)  # a copy: cluster_centers_ is the caller's to change
+
+
 class KMeans:
     """Drop-in for ``sklearn.cluster.KMeans`` (lloyd) on the MI355X kernels.
 
     ``fit`` accepts a host array (standardised features, as MILWRM passes
     ``cluster_data``) or ``DeviceRows`` (HBM-resident rows with the scaler
     folded in).  Fitted attributes match sklearn's: ``cluster_centers_``
-    (fp64), ``labels_`` (int32), ``inertia_``, ``n_iter_``."""
+    (fp64), ``labels_`` (int32), ``inertia_``, ``n_iter_``.
+
+    A fit through the C driver leaves its final pass over the rows (the
+    extra E-step and the inertia) to the first read of ``labels_`` or
+    ``inertia_`` (or ``finalize()``), and keeps the rows alive until then:
+    a caller that needs the centers only never pays that pass."""
 
     def __init__(self, n_clusters=8, *, init="k-means++", n_init="auto", max_iter=300, tol=1e-4,
                  verbose=0, random_state=None, copy_x=True, algorithm="lloyd"):
@@ -965,11 +983,19 @@ class KMeans:
                 best = (labels, inertia, centers, n_iter)
         return self._set_fitted(rows, *best)
 
-    def _fit_c(self, rows, k, init):
+    def _fit_c(self, rows, k, init, defer=True):
         """The whole fit in the C++ driver (mw_kmeans_fit, csrc/fit.cpp): the
         same control flow and fp64 host arithmetic as the Python path below
         (bitwise the same result, tests/test_gpu_fit_c.py), without a Python
-        round trip per Lloyd iteration."""
+        round trip per Lloyd iteration.
+
+        ``defer``: the fit stops after its last Lloyd iteration
+        (mw_kmeans_fit_deferred); the final pass over the rows -- the extra
+        E-step and the inertia -- runs when ``labels_``, ``inertia_`` or
+        ``finalize()`` ask for it (``_finish``), the same bits then.  The
+        label pass over the slides needs the centers only and never asks.
+        ``defer=False``: that pass queued behind the fit
+        (mw_kmeans_fit_async_moments)."""
         S, F = rows.S, rows.F
         mu = np.ascontiguousarray(rows.mu, dtype=np.float64)
         inv = np.ascontiguousarray(rows.inv, dtype=np.float64)
@@ -990,13 +1016,32 @@ class KMeans:
 
         RESIDENCY.release(nb + S + (64 << 20))  # workspace + labels; host-backed slide copies go first
         ws = D.WS.get("kfit", nb)
+        # a k-means++ seeding of rows that carry their moment records starts
+        # from them (mw_kpp_init_moments) instead of the init pass
+        segs = rows.moment_segments() if c0 is None and k >= 2 else None
+        if defer:
+            if xmax is None:  # the finish needs the column maxima the fit would take itself
+                m = torch.empty(F, dtype=torch.float32, device=rows.X.device)
+                N.call("mw_col_absmax", D.P(rows.X), S, F, D.P(m), D.stream())
+                xmax = np.ascontiguousarray(D.d2h(m), np.float32)
+            strict = C.c_int()
+            with profiling.timed("kmeans_fit", 0):
+                N.call("mw_kmeans_fit_deferred", D.P(rows.X), S, F, mu.ctypes.data, inv.ctypes.data,
+                       None if var is None else var.ctypes.data, xmax.ctypes.data, k,
+                       None if c0 is None else c0.ctypes.data,
+                       0 if c0 is not None else int(self.random_state),  # unused with an array init
+                       int(self.max_iter), float(self.tol or 0.0), D.P(labels), centers.ctypes.data,
+                       C.addressof(n_iter), idx.ctypes.data, D.P(ws), ws.numel(),
+                       0 if segs is None else segs[0], None if segs is None else C.addressof(segs[1]),
+                       C.addressof(strict), D.stream())
+            if c0 is None:
+                KPP_INIT_USED["moments" if segs is not None else "pass"] += 1
+            self.init_indices_ = None if c0 is not None else idx
+            return labels, _Deferred(rows.X, mu, inv, xmax, strict.value != 0, centers), centers, n_iter.value
         # the final E-step's record lands here when the stream gets there: the
         # fit returns with that pass queued, so whatever the caller queues next
         # (the label pass) follows it without a host round trip (_Inertia)
         rec = torch.empty(N.query("mw_lloyd_rec_len", k, F), dtype=torch.float64, pin_memory=True)
-        # a k-means++ seeding of rows that carry their moment records starts
-        # from them (mw_kpp_init_moments) instead of the init pass
-        segs = rows.moment_segments() if c0 is None and k >= 2 else None
         with profiling.timed("kmeans_fit", 0):
             N.call("mw_kmeans_fit_async_moments", D.P(rows.X), S, F, mu.ctypes.data, inv.ctypes.data,
                    None if var is None else var.ctypes.data,
@@ -1024,19 +1069,67 @@ class KMeans:
         return _kmeans_plusplus_device(rows, int(self.n_clusters), rs, moments=moments)
 
     def _set_fitted(self, rows, labels, inertia, centers, n_iter):
-        self._labels_dev = labels
+        """``inertia``: a float, an ``_Inertia`` (final pass queued) or a
+        ``_Deferred`` (final pass not queued: ``_finish``)."""
+        self._labels_buf = labels
         self.cluster_centers_ = centers
-        self._inertia = inertia
+        self._pending = inertia if isinstance(inertia, _Deferred) else None
+        self._inertia = None if self._pending is not None else inertia
         self.n_iter_ = n_iter
         self.n_features_in_ = rows.F
         self._n_features_out = int(self.n_clusters)
         self._labels_host = None
         return self
 
+    def _finish(self):
+        """The final pass of a deferred fit (mw_kmeans_fit_finish), once: the
+        extra E-step into the label buffer unless the fit converged strictly,
+        and the inertia's record.  Until it has run the label buffer holds the
+        last iteration's labels, which nothing hands out.  The rows are let go
+        afterwards."""
+        d = getattr(self, "_pending", None)
+        if d is None:
+            return
+        S, F = d.X.shape
+        centers = d.centers
+        k = centers.shape[0]
+        ws = D.WS.get("kfit_finish", N.query("mw_kmeans_fit_finish_ws_bytes", S, F, k))
+        rec = torch.empty(N.query("mw_lloyd_rec_len", k, F), dtype=torch.float64, pin_memory=True)
+        iexp = C.c_int()
+        with profiling.timed("kmeans_finish", S * F * 4):
+            N.call("mw_kmeans_fit_finish", D.P(d.X), S, F, d.mu.ctypes.data, d.inv.ctypes.data,
+                   d.xmax.ctypes.data, k, centers.ctypes.data, int(d.strict), D.P(self._labels_buf), D.P(ws),
+                   ws.numel(), rec.data_ptr(), C.addressof(iexp), D.stream())
+            done = torch.cuda.Event()
+            done.record()
+        self._pending = None
+        FIT_FINISH_USED["finish"] += 1
+        if self._inertia is None:
+            self._inertia = _Inertia(done, rec, iexp.value)
+
+    def finalize(self):
+        """Run what a deferred fit left out (the final pass over the rows:
+        ``labels_`` and ``inertia_``) now, and let the rows go.  No-op when
+        nothing is pending."""
+        self._finish()
+        return self
+
+    @property
+    def _labels_dev(self) -> torch.Tensor:
+        """The sample's labels under the final centers (uint8, device)."""
+        self._finish()
+        return self._labels_buf
+
+    @_labels_dev.setter
+    def _labels_dev(self, v):
+        self._labels_buf = v
+
     @property
     def inertia_(self) -> float:
-        """sklearn's inertia_ (a fit through mw_kmeans_fit_async reads its final
-        record on first access, after the stream has reached it)."""
+        """sklearn's inertia_ (a deferred fit runs its final pass on first
+        access; a fit through mw_kmeans_fit_async reads its final record then,
+        after the stream has reached it)."""
+        self._finish()
         if isinstance(self._inertia, _Inertia):
             self._inertia = self._inertia.value()
         return self._inertia
