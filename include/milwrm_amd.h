@@ -17,7 +17,8 @@
  *                      scipy.ndimage.gaussian_filter       MxIF.py:375-394
  *   mw_clahe           img.equalize_hist → skimage equalize_adapthist
  *                                                          MxIF.py:95-122, 360-373
- *   mw_block_mean      img.downsample → skimage block_reduce MxIF.py:494-517
+ *   mw_block_mean,
+ *   mw_block_reduce_rows img.downsample → skimage block_reduce MxIF.py:494-517
  *   mw_mask_rank,
  *   mw_gather_rows     img.subsample_pixels (mask gather + fancy index)
  *                                                          MxIF.py:457-492
@@ -261,6 +262,30 @@ int mw_blur(const void* d_img, int dtype, int H, int W, int C,
  * included.  HWC in, fp32 HWC out of ceil(H/f) x ceil(W/f) x C. */
 int mw_block_mean(const void* d_img, int dtype, int H, int W, int C, int fact,
                   float* d_out, void* stream);
+
+/* ---- img.downsample(fact, func) on a slide or a row band of it --------------
+ * skimage block_reduce(x, (fact, fact, 1), func, cval=0): the pad (zeros below
+ * the slide's last row and right of its last column) takes part in every func.
+ * d_rows holds the slide's rows [row0, row0 + rows), HWC; d_out is the whole
+ * ceil(slide_H / fact) x ceil(W / fact) x C fp32 result, of which the call
+ * writes the output rows from row0 / fact on.  row0 must be a multiple of
+ * fact, and so must rows unless the band ends at slide_H (MW_EINVAL
+ * otherwise); a resident slide is the one-band case.  Every output value is
+ * computed from its own block in one order, so the result has the same bits
+ * whatever the band split: mean and sum in fp64, block rows top to bottom and
+ * within a row left to right, rounded once (mean: the bits of the block-mean
+ * entry above); max and min exact, a NaN in the block gives NaN; median the
+ * exact middle order statistic, an even count the fp64 average of the middle
+ * two, any NaN gives NaN, fact <= 16 (MW_EUNSUPPORTED above, nothing
+ * launched). */
+#define MW_REDUCE_MEAN 0
+#define MW_REDUCE_SUM 1
+#define MW_REDUCE_MAX 2
+#define MW_REDUCE_MIN 3
+#define MW_REDUCE_MEDIAN 4
+int mw_block_reduce_rows(const void* d_rows, int dtype, int rows, int W, int C,
+                         int row0, int slide_H, int fact, int func,
+                         float* d_out, void* stream);
 
 /* ---- mask row-major rank → pixel (MxIF.py:486-488) --------------------------
  * d_rank2pix[r] = flat index of the r-th pixel with mask != 0.  d_count gets

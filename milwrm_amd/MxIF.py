@@ -98,7 +98,8 @@ class _DeviceMask:
     def __init__(self, t):
         self._t = t
         self.shape = tuple(t.shape)
-        self.dtype = np.dtype(np.uint8)
+        # (a mask that img.downsample reduced on the device is fractional: fp32)
+        self.dtype = np.dtype(np.float32 if t.dtype == torch.float32 else np.uint8)
 
     def __array__(self, dtype=None, copy=None):
         a = self._t.cpu().numpy()
@@ -207,7 +208,8 @@ class img:
                 f"this operation needs the whole raw slide in HBM ({nbytes / 2**30:.1f} GiB) and "
                 f"{have / 2**30:.1f} GiB can be allocated: the slide is streamed in row bands instead by "
                 f"the passes that take bands (calculate_non_zero_mean, log_normalize + blurring with the "
-                f"default batch mean, subsample_pixels, label_tissue_regions, confidence_score_images)")
+                f"default batch mean, subsample_pixels, create_tissue_mask, downsample, label_tissue_regions, "
+                f"confidence_score_images)")
 
     def _source(self):
         """None when the raw pixels are resident (or are admitted now: the
@@ -958,14 +960,40 @@ class img:
         return X.double().cpu().numpy()
 
     def downsample(self, fact, func=np.mean):
-        """MxIF.py:494-517 with func=np.mean (block_reduce, zero padded, pad
-        zeros counted); the mask becomes fractional exactly as the reference."""
-        if func is not np.mean:
-            raise NotImplementedError("downsample supports func=np.mean on the device")
-        if self.mask is not None:
-            m = torch.from_numpy(np.ascontiguousarray(self.mask, dtype=np.float32)[:, :, None]).to(D.device())
-            self.mask = D.block_mean(m, int(fact))[:, :, 0].double().cpu().numpy()
-        out = D.block_mean(self._materialize(), int(fact))
+        """MxIF.py:494-517: skimage ``block_reduce(img, (fact, fact, 1), func,
+        cval=0)`` for func = np.mean, np.sum, np.max, np.min or np.median (zero
+        padded, the pad's zeros take part); the mask goes through the same
+        func, as in the reference (np.mean: it becomes fractional).  A slide
+        that is not resident is reduced band by band (stream.downsample), any
+        pending log_normalize or deferred filter applied to each band first:
+        the bits are the resident slide's.  A host mask comes back as a float64
+        array; a device mask stays on the device as fp32."""
+        from . import stream
+
+        func = D.reduce_func(func)
+        fact = D.reduce_fact(fact)
+        if getattr(self, "_band", None) is not None:
+            raise NotImplementedError("downsample of a row band of a slide split over ranks "
+                                      "(the blocks straddle the bands)")
+        src = self._source()
+        if src is not None:
+            filt = stream.band_filter(self)
+            if filt is None and self._pending is not None and self._pending[0] is not None:
+                filt = stream.LogNormBand(*self._pending)
+            out = stream.downsample(src, fact, func, filt)
+            self._pending = self._pending_blur = self._pending_median = self._pending_bilateral = None
+            self._lognorm_host = None
+        else:
+            out = D.block_reduce(self._materialize(), fact, func)
+        m = self._mask
+        if isinstance(m, _DeviceMask):
+            t = m._t if m._t.dtype in (torch.uint8, torch.float32) else m._t.to(torch.float32)
+            small = D.block_reduce(t.contiguous()[:, :, None], fact, func)[:, :, 0]
+            self.mask = _DeviceMask(small)
+            self._mask_dev = D.padded_mask((small != 0).to(torch.uint8))
+        elif m is not None:
+            t = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)[:, :, None]).to(D.device())
+            self.mask = D.block_reduce(t, fact, func)[:, :, 0].double().cpu().numpy()
         self._set_device(out)
         self._xbound = None
 
@@ -1014,12 +1042,20 @@ class img:
         random_state=18) on the UNscaled samples, predict every pixel on ALL
         channels (as the reference's ``kmeans.predict(image_ar_reshape)``, so a
         feature subset raises sklearn's feature-count error), background flip."""
-        from .assign import assign_image
+        from .assign import assign_image, banded_assign_image
         from .kmeans import DeviceRows, KMeans
+        from .stream import band_filter
 
         cp = self.copy()
         H, W = cp.shape[0], cp.shape[1]
-        cp.mask = np.ones((H, W))
+        if cp._source() is not None:
+            # a slide read band by band: the all-ones mask lives on the device (as float64 on
+            # the host it would be 8 bytes per pixel of a slide too large to hold)
+            ones = torch.ones((H, W), dtype=torch.uint8, device=D.device())
+            cp.mask = _DeviceMask(ones)
+            cp._mask_dev = D.padded_mask(ones)
+        else:
+            cp.mask = np.ones((H, W))
         cp.log_normalize()
         cp.blurring("gaussian", sigma=2)
         X, st = cp._subsample_device(features, fract)
@@ -1030,9 +1066,16 @@ class img:
         d = cp.n_ch
         if d != F:
             raise ValueError(f"X has {d} features, but KMeans is expecting {F} features as input.")
-        lab, _, _ = assign_image(D.as_float32(cp._materialize()), list(range(d)), np.zeros(F),
-                                 np.ones(F), km.cluster_centers_, cp._mask_device())
-        tID = lab.cpu().numpy().astype(float)
+        res = None
+        if cp._filter_deferred():
+            # the blur was deferred (a slide that is not resident, or whose fp32 copy would not fit):
+            # labelled band by band, the whole-slide bits (assign.banded_assign_image)
+            res = banded_assign_image(cp._source() or cp._device(), band_filter(cp), list(range(d)), np.zeros(F),
+                                      np.ones(F), km.cluster_centers_, cp._mask_device())
+        if res is None:
+            res = assign_image(D.as_float32(cp._materialize()), list(range(d)), np.zeros(F),
+                               np.ones(F), km.cluster_centers_, cp._mask_device())
+        tID = res[0].cpu().numpy().astype(float)
         scores = km.cluster_centers_
         z = (scores - scores.mean()) / scores.std()
         if z[0].mean() > 0:

@@ -639,6 +639,56 @@ def block_mean(img: torch.Tensor, fact: int):
     return out
 
 
+# img.downsample's funcs (include/milwrm_amd.h: MW_REDUCE_*)
+REDUCE_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "median": 4}
+_REDUCE_FUNCS = ((np.mean, "mean"), (np.sum, "sum"), (np.max, "max"), (np.min, "min"), (np.median, "median"))
+
+
+def reduce_func(func) -> str:
+    """The name of a ``downsample`` func: np.mean, np.sum, np.max / np.amax,
+    np.min / np.amin, np.median, or one of their names."""
+    if isinstance(func, str) and func in REDUCE_CODES:
+        return func
+    for f, name in _REDUCE_FUNCS:
+        if func is f or (name in ("max", "min") and func is getattr(np, "a" + name)):
+            return name
+    raise NotImplementedError("downsample supports func = np.mean, np.sum, np.max (np.amax), np.min (np.amin) "
+                              f"or np.median on the device, got {func!r}")
+
+
+def reduce_fact(fact) -> int:
+    """``downsample``'s block size: an int >= 1."""
+    if isinstance(fact, (bool, np.bool_)) or not isinstance(fact, (int, np.integer)) or fact < 1:
+        raise ValueError(f"downsample: fact must be an int >= 1, got {fact!r}")
+    return int(fact)
+
+
+def block_reduce_rows(rows: torch.Tensor, row0: int, slide_H: int, fact: int, func, out: torch.Tensor):
+    """The slide's rows [row0, row0 + len(rows)) (HWC) reduced into their rows
+    of ``out``, the whole ceil(slide_H / fact) x ceil(W / fact) x C fp32
+    result (mw_block_reduce_rows: ``row0`` and, unless the band ends the
+    slide, its height are multiples of ``fact``)."""
+    name, fact = reduce_func(func), reduce_fact(fact)
+    H, W, C = rows.shape
+    if not rows.is_contiguous() or not out.is_contiguous():
+        raise ValueError("block_reduce_rows: the rows and the result must be contiguous")
+    if tuple(out.shape) != (-(-slide_H // fact), -(-W // fact), C) or out.dtype != torch.float32:
+        raise ValueError(f"block_reduce_rows: the result is {tuple(out.shape)} {out.dtype}")
+    with profiling.timed("block_reduce", H * W * C * rows.element_size() + -(-H // fact) * out.shape[1] * C * 4):
+        N.call("mw_block_reduce_rows", P(rows), dtype_code(rows), H, W, C, int(row0), int(slide_H), fact,
+               REDUCE_CODES[name], P(out), stream())
+    return out
+
+
+def block_reduce(img: torch.Tensor, fact: int, func=np.mean):
+    """skimage ``block_reduce(img, (fact, fact, 1), func, cval=0)`` of a
+    resident HWC tensor as fp32: the one-band case of ``block_reduce_rows``."""
+    fact = reduce_fact(fact)
+    H, W, C = img.shape
+    out = torch.empty((-(-H // fact), -(-W // fact), C), dtype=torch.float32, device=img.device)
+    return block_reduce_rows(img.contiguous(), 0, H, fact, func, out)
+
+
 class RankIndex:
     """The mask rank of a slide as the compact index of mw_mask_rank_index
     (per 64-pixel word: mask bits and the tissue pixels before it; ~n/6
@@ -768,7 +818,7 @@ def col_stats_rows(X: torch.Tensor, stats: torch.Tensor, accumulate: bool, absma
 
 # deferred-filter paths taken (blur or median; tests read it); *_streamed: over a slide read band by band (stream.py)
 FUSED_USED = {"sample": 0, "assign": 0, "assign_banded": 0, "sample_streamed": 0, "assign_streamed": 0,
-              "nz_streamed": 0}
+              "nz_streamed": 0, "downsample_streamed": 0}
 # median paths taken (tests read it): the register selection network or the generic rank search;
 # rows_streamed: bands filtered from a slide that is not resident (stream.MedianBand)
 MEDIAN_USED = {"network": 0, "generic": 0, "rows_streamed": 0}

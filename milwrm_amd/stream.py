@@ -15,7 +15,7 @@ Here:
   does a pass that needs HBM for its own buffers (``Residency.release``);
 * an image that is not resident is STREAMED: every pass that needs its
   pixels (non-zero statistics, blur + subsample, blur + label/confidence,
-  the QC sums) reads it as row bands (``band_rows`` rows plus the blur's
+  the QC sums, the downsample) reads it as row bands (``band_rows`` rows plus the blur's
   halo rows above and below), double-buffered: band b+1 is read on a side
   stream (host-to-device copy, or the synthetic generator standing in for a
   slide reader) while band b is processed;
@@ -397,7 +397,13 @@ def _side_stream(dev) -> torch.cuda.Stream:
     return s
 
 
-def _plan(H, band_rows, halo, r0, r1):
+def _plan(H, band_rows, halo, r0, r1, quantum=1):
+    """(y0, y1, a, b) per band: output rows [y0, y1) of [r0, r1) from the slide
+    rows [a, b) (the halo clipped to the slide).  ``quantum`` > 1: the bands
+    are whole multiples of it high (at least one), so every band starts a
+    multiple of ``quantum`` rows after ``r0`` (block passes: stream.downsample)."""
+    if quantum > 1:
+        band_rows = max(quantum, band_rows // quantum * quantum)
     plan = []
     for y0 in range(r0, r1, max(1, band_rows)):
         y1 = min(r1, y0 + band_rows)
@@ -405,7 +411,7 @@ def _plan(H, band_rows, halo, r0, r1):
     return plan
 
 
-def bands(src: RowSource, band_rows: int, halo: int, r0: int = 0, r1=None):
+def bands(src: RowSource, band_rows: int, halo: int, r0: int = 0, r1=None, quantum: int = 1):
     """Yield (y0, y1, a, raw): output rows [y0, y1) of [r0, r1) in bands of
     ``band_rows``, ``raw`` = the device rows [a, a + len(raw)) = [y0 - halo,
     y1 + halo) clipped to the slide.  A resident source yields views; any
@@ -413,13 +419,15 @@ def bands(src: RowSource, band_rows: int, halo: int, r0: int = 0, r1=None):
     caller's work on band b runs on the current stream.  When HBM cannot hold
     two buffers of ``band_rows`` + 2 halo rows, the bands get lower
     (``alloc_rows``); every output row is computed the same way whatever
-    band holds it.  The side stream's reads are ordered before the main
+    band holds it; with ``quantum`` > 1 the bands, lowered ones too, stay
+    whole multiples of ``quantum`` rows.  The side stream's reads are ordered
+    before the main
     stream's later work also when the consumer stops early (an exception, or
     a caller that abandons the generator), so the buffers are never handed
     back to the allocator while a read into them is in flight."""
     H = src.H
     r1 = H if r1 is None else r1
-    plan = _plan(H, band_rows, halo, r0, r1)
+    plan = _plan(H, band_rows, halo, r0, r1, quantum)
     if src.zero_copy:
         for y0, y1, a, b in plan:
             yield y0, y1, a, src.read(a, b, None)
@@ -430,14 +438,14 @@ def bands(src: RowSource, band_rows: int, halo: int, r0: int = 0, r1=None):
     rows = max(b - a for _, _, a, b in plan)
     nbuf = min(2, len(plan))
     RESIDENCY.release(nbuf * rows * src.row_bytes + (256 << 20))
-    lo = min(rows, 2 * halo + 1)
+    lo = min(rows, 2 * halo + max(1, quantum))
     bufs = [alloc_rows(rows, (src.W, src.C), src.dtype, min_rows=lo, dev=dev)]
     if nbuf > 1:
         bufs.append(alloc_rows(int(bufs[0].shape[0]), (src.W, src.C), src.dtype, min_rows=lo, dev=dev))
     got = min(int(b.shape[0]) for b in bufs)
     while got < rows:  # HBM was short: lower bands into the buffers that could be had
         rows = got
-        plan = _plan(H, max(1, got - 2 * halo), halo, r0, r1)
+        plan = _plan(H, max(1, got - 2 * halo), halo, r0, r1, quantum)
         if len(plan) > 1 and len(bufs) < 2:  # a one-band plan became several: try for a second buffer
             try:
                 bufs.append(alloc_rows(got, (src.W, src.C), src.dtype, min_rows=min(got, lo), dev=dev))
@@ -568,6 +576,20 @@ class BilateralBand:
                                 out=out_f32[:y1 - y0])
 
 
+class LogNormBand:
+    """A pending log_normalize alone as a band filter (no halo): the band
+    through ``device.lognorm``, element by element the whole slide's bits."""
+
+    halo = 0
+
+    def __init__(self, inv_mean, pseudoval: float = 1.0):
+        self.inv_mean, self.pseudoval = inv_mean, pseudoval
+        self.streamed = False
+
+    def rows(self, raw, a, y0, y1, H, out_f32):
+        return D.lognorm(raw[y0 - a:y1 - a], self.inv_mean, self.pseudoval, out=out_f32[:y1 - y0])
+
+
 def band_filter(image):
     """The band filter of an ``img`` whose filter is deferred (Gaussian,
     median or bilateral, with the pending log_normalize as its prologue /
@@ -582,14 +604,54 @@ def band_filter(image):
     return None
 
 
-def filtered_bands(src, filt, band_rows: int, buf: torch.Tensor, r0: int = 0, r1=None):
+def filtered_bands(src, filt, band_rows: int, buf: torch.Tensor, r0: int = 0, r1=None, quantum: int = 1):
     """Yield (y0, y1, core): the fp32 rows [y0, y1) of ``filt`` over the slide
-    ``src``, band after band of ``bands(src, band_rows, filt.halo, r0, r1)``,
-    through the reused fp32 band buffer ``buf`` (band_rows + 2 halo rows)."""
+    ``src``, band after band of ``bands(src, band_rows, filt.halo, r0, r1,
+    quantum)``, through the reused fp32 band buffer ``buf`` (band_rows + 2 halo
+    rows)."""
     src = as_source(src)
     filt.streamed = not src.zero_copy
-    for y0, y1, a, raw in bands(src, band_rows, filt.halo, r0, r1):
+    for y0, y1, a, raw in bands(src, band_rows, filt.halo, r0, r1, quantum):
         yield y0, y1, filt.rows(raw, a, y0, y1, src.H, buf)
+
+
+def downsample(src, fact: int, func=np.mean, filt=None) -> torch.Tensor:
+    """``device.block_reduce`` of a slide band after band (``img.downsample``
+    of a slide that is not resident): the fp32 ceil(H / fact) x ceil(W / fact)
+    x C result, each band of whole block rows reduced into its output rows
+    (mw_block_reduce_rows).  ``filt``: a band filter applied to the rows first
+    (a deferred Gaussian, median or bilateral, or ``LogNormBand``).  Every
+    output value comes from its own block in one order, so the bits are the
+    resident slide's whatever the bands.  MemoryError when HBM cannot hold the
+    result."""
+    src = as_source(src)
+    func, fact = D.reduce_func(func), D.reduce_fact(fact)
+    H, W, C = src.shape
+    Ho, Wo = -(-H // fact), -(-W // fact)
+    nbytes = Ho * Wo * C * 4
+    RESIDENCY.release(nbytes + (256 << 20))
+    have = alloc_bytes()
+    if nbytes + (256 << 20) > have:
+        raise MemoryError(
+            f"downsample(fact={fact}): the {Ho} x {Wo} x {C} fp32 result takes {nbytes / 2**30:.2f} GiB and "
+            f"{have / 2**30:.2f} GiB can be allocated: use a larger fact")
+    out = torch.empty((Ho, Wo, C), dtype=torch.float32, device=D.device())
+    halo = 0 if filt is None else filt.halo
+    band_rows = band_rows_for(src, 0 if filt is None else W * C * 4)
+    band_rows = min(-(-H // fact) * fact, max(fact, band_rows // fact * fact))
+    if filt is None:
+        for y0, _, _, raw in bands(src, band_rows, 0, quantum=fact):
+            D.block_reduce_rows(raw, y0, H, fact, func, out)
+    else:
+        want = min(H, band_rows + 2 * halo)
+        buf = alloc_rows(want, (W, C), torch.float32, min_rows=min(want, fact + 2 * halo))
+        if int(buf.shape[0]) < want:  # HBM was short: lower bands, still whole block rows
+            band_rows = max(fact, (int(buf.shape[0]) - 2 * halo) // fact * fact)
+        for y0, _, core in filtered_bands(src, filt, band_rows, buf, quantum=fact):
+            D.block_reduce_rows(core, y0, H, fact, func, out)
+    if not src.zero_copy:
+        D.FUSED_USED["downsample_streamed"] += 1
+    return out
 
 
 def _band_gather(src, filt, feat: torch.Tensor, idx: torch.Tensor, r2p, X_out: torch.Tensor, band_rows,
