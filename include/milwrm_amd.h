@@ -92,6 +92,34 @@ size_t mw_quantiles_ws_bytes(int C, int nq);
 int mw_quantiles(const void* d_img, int dtype, int64_t n_pix, int C,
                  int pooled, const double* h_q, int nq, int skip_sentinel,
                  double* d_out, void* d_ws, void* stream);
+/* The same selection over a slide that is handed over in bands of rows (a
+ * slide streamed from the host, stream.quantiles): mw_quantiles is
+ * begin, then per pass one count and one choose.
+ *   mw_quantiles_passes      passes of a dtype (1 u8, 2 u16, 4 fp32; 0: bad dtype)
+ *   mw_quantiles_rows_begin  zeroes the workspace (mw_quantiles_ws_bytes(C, nq))
+ *   mw_quantiles_rows_count  adds the n_pix pixels at d_rows to the histograms
+ *                            of pass `pass` (and, in pass 0, to the NaN counts);
+ *                            once per band, every band in every pass
+ *   mw_quantiles_rows_choose once per pass after its last band: the digit of
+ *                            every rank; the last pass writes d_out as
+ *                            mw_quantiles does
+ * The counts are integer adds, so the record is bit for bit mw_quantiles' of
+ * the whole slide whatever the bands and their order.  d_rows must start a
+ * pixel (element 0 = channel 0) and be aligned to its element type only: a
+ * band that is a view into a resident slide starts at y * W * C elements,
+ * and the kernel leaves out what precedes it in its first 16-byte vector
+ * (up to 15 bytes below d_rows are loaded, inside the same aligned 16 bytes).
+ * pooled, skip_sentinel, nq, h_q and C as mw_quantiles, the same values in
+ * every call of one selection.  Nothing returns to the host between the calls;
+ * all of them on one stream (or ordered by the caller). */
+int mw_quantiles_passes(int dtype);
+int mw_quantiles_rows_begin(int C, int pooled, int nq, void* d_ws, void* stream);
+int mw_quantiles_rows_count(const void* d_rows, int dtype, int64_t n_pix, int C,
+                            int pooled, int nq, int skip_sentinel, int pass,
+                            void* d_ws, void* stream);
+int mw_quantiles_rows_choose(int dtype, int C, int pooled, const double* h_q,
+                             int nq, int pass, double* d_out, void* d_ws,
+                             void* stream);
 /* Elementwise intensity rescale, fp32 out (may alias an fp32 in).  d_params
  * (device, [C][5] doubles): lo, hi, omin, omax, mode with mode 0 = the value
  * itself, 1 = (clip(x, lo, hi) - lo) / (hi - lo) * (omax - omin) + omin,

@@ -67,7 +67,7 @@ def _module_call(image, op, channels, **kwargs):
     a = np.asarray(image)
     im = img(a)
     getattr(im, op)(channels=channels, **kwargs)
-    out = im._dev.cpu().numpy()
+    out = im._materialize().cpu().numpy()  # (the op may have stayed deferred: a slide over the HBM budget)
     return out if a.ndim > 2 else out[:, :, 0]
 
 
@@ -118,6 +118,10 @@ class img:
         self._host = np.asarray(img_arr)
         self._host64 = None
         self._dev = None            # HWC device tensor (authoritative when set)
+        # deferred clip / scale rounds, applied before anything else pending (stream.RescaleSource):
+        # (host [C, 5] D.rescale tables, the same on the device)
+        self._pending_rescale = None
+        self._range = None          # per-channel (lo, hi) of clipped / scaled pixels (NaN: not known), see _blur_bound
         self._pending = None        # (inv_mean fp32 device tensor, pseudoval) deferred log_normalize
         self._pending_blur = None   # (sigma, truncate) deferred gaussian (fused-epilogue mode)
         self._pending_median = None  # (size_y, size_x) deferred median (applied band by band, stream.MedianBand)
@@ -169,6 +173,8 @@ class img:
         """Bytes per element of the pixels as the device holds (or would hold) them."""
         from .stream import device_dtype_of
 
+        if self._pending_rescale is not None:
+            return 4
         if self._dev is not None:
             return self._dev.element_size()
         t = self._src.dtype if self._host is None else device_dtype_of(self._host)
@@ -207,14 +213,28 @@ class img:
             raise MemoryError(
                 f"this operation needs the whole raw slide in HBM ({nbytes / 2**30:.1f} GiB) and "
                 f"{have / 2**30:.1f} GiB can be allocated: the slide is streamed in row bands instead by "
-                f"the passes that take bands (calculate_non_zero_mean, log_normalize + blurring with the "
+                f"the passes that take bands (clip and scale of raw or clipped / scaled pixels, "
+                f"calculate_non_zero_mean, log_normalize + blurring with the "
                 f"default batch mean, subsample_pixels, create_tissue_mask, downsample, label_tissue_regions, "
-                f"confidence_score_images)")
+                f"confidence_score_images; not clip or scale after a log_normalize or a filter, nor "
+                f"equalize_hist)")
 
     def _source(self):
-        """None when the raw pixels are resident (or are admitted now: the
-        caller then takes ``_device()``); else the ``stream.RowSource`` to read
-        them from band by band."""
+        """None when the pixels are resident (or the raw ones are admitted now:
+        the caller then takes ``_device()``); else the ``stream.RowSource`` to
+        read them from band by band.  With clip / scale rounds deferred that is
+        always a source: the raw one -- the resident raw slide, if it is --
+        seen through the rounds (``stream.RescaleSource``)."""
+        from .stream import DeviceSource, RescaleSource
+
+        base = self._raw_source()
+        if self._pending_rescale is None:
+            return base
+        return RescaleSource(base if base is not None else DeviceSource(self._device()),
+                             self._pending_rescale[1])
+
+    def _raw_source(self):
+        """``_source`` of the raw pixels (before any deferred clip / scale)."""
         from .stream import RESIDENCY, HostSource
 
         if self._dev is not None:
@@ -251,6 +271,8 @@ class img:
         obj._host = None
         obj._host64 = None
         obj._dev = None
+        obj._pending_rescale = None
+        obj._range = None
         obj._pending = None
         obj._pending_blur = None
         obj._pending_median = None
@@ -281,7 +303,13 @@ class img:
         """Apply a deferred blur (with its log_normalize fused), a deferred
         median (the log_normalize as its epilogue), a deferred bilateral (the
         log_normalize as its load) or a deferred log_normalize (standalone
-        kernel)."""
+        kernel).  Deferred clip / scale rounds apply first, then what else
+        is pending on their fp32 result, as one evictable transform."""
+        if self._pending_rescale is not None:
+            rng = self._range if self._pending is None and not self._filter_deferred() else None
+            self._transformed(self._apply_rescaled)
+            self._range = rng
+            return self._device()
         if self._pending_bilateral is not None:
             sigma, sigma_color, win_size, mode, cval = self._pending_bilateral
             inv, p = self._pending if self._pending is not None else (None, 1.0)
@@ -312,6 +340,24 @@ class img:
                 self._transformed(lambda: D.lognorm(self._device(), inv, p))
         return self._device()
 
+    def _apply_rescaled(self) -> torch.Tensor:
+        """The pixels with everything pending applied, the deferred clip /
+        scale rounds first: the calls of the resident path, in its order."""
+        t = self._device()  # (a slide that is not resident and does not fit: _device()'s MemoryError)
+        for i, tab in enumerate(self._pending_rescale[1]):
+            t = D.rescale(t, tab, out=t if i else None)
+        inv, p = self._pending if self._pending is not None else (None, 1.0)
+        if self._pending_bilateral is not None:
+            sigma, sigma_color, win_size, mode, cval = self._pending_bilateral
+            return D.bilateral_rows(t, sigma, sigma_color, 0, t.shape[0], 0, t.shape[0], win_size=win_size,
+                                    mode=mode, cval=cval, inv_mean=inv, pseudoval=p)
+        if self._pending_median is not None:
+            return D.median(t, self._pending_median, inv_mean=inv, pseudoval=p)
+        if self._pending_blur is not None:
+            sigma, truncate = self._pending_blur
+            return D.blur(t, sigma, inv_mean=inv, pseudoval=p, truncate=truncate)
+        return t if inv is None else D.lognorm(t, inv, p)
+
     def _transformed(self, make):
         """Replace the pixels by ``make()`` (the pending transforms applied).
         An image backed by a host array or a source keeps how to redo it: its
@@ -321,8 +367,9 @@ class img:
 
         backed = self._host is not None or self._src is not None
         state = (self._host, self._src, self._pending, self._pending_blur,
-                 self._pending_median, self._pending_bilateral) if backed else None
+                 self._pending_median, self._pending_bilateral, self._pending_rescale, self._range) if backed else None
         out = make()
+        self._pending_rescale = None
         self._pending = None
         self._pending_blur = None
         self._pending_median = None
@@ -344,6 +391,7 @@ class img:
         self._src = None
         self._hsrc = None
         self._revert = None
+        self._range = None
 
     def _evict(self):
         """Drop the device copy: the raw copy of a host array / source, or a
@@ -351,7 +399,7 @@ class img:
         rv = getattr(self, "_revert", None)
         if rv is not None:
             (self._host, self._src, self._pending, self._pending_blur, self._pending_median,
-             self._pending_bilateral) = rv
+             self._pending_bilateral, self._pending_rescale, self._range) = rv
             self._revert = None
             self._host64 = None
         self._dev = None
@@ -362,7 +410,7 @@ class img:
         if self._host64 is None:
             if (self._dev is None and self._host is not None and self._pending is None
                     and self._pending_blur is None and self._pending_median is None
-                    and self._pending_bilateral is None):
+                    and self._pending_bilateral is None and self._pending_rescale is None):
                 self._host64 = self._host.astype("float64")
             else:
                 t = self._materialize()
@@ -382,6 +430,8 @@ class img:
         self._dev = None
         self._src = None
         self._hsrc = None
+        self._pending_rescale = None
+        self._range = None
         self._pending = None
         self._pending_blur = None
         self._pending_median = None
@@ -477,6 +527,8 @@ class img:
         obj._host = None
         obj._host64 = None
         obj._dev = tensor
+        obj._pending_rescale = None
+        obj._range = None
         obj._pending = None
         obj._pending_blur = None
         obj._pending_median = None
@@ -565,30 +617,80 @@ class img:
                 todo.remove(c)
         return rounds
 
-    def _intensity(self, channels, select, rows_of):
-        """clip / scale: pending transforms applied, then per round one exact
-        selection (D.quantiles, one host read of its few numbers) and one
-        rescale pass.  ``select(t, pooled)`` queues the selection;
-        ``rows_of(record)`` turns a channel's record into its D.rescale row.
-        A channel listed twice is processed twice, as the reference's loop
-        does."""
+    def _intensity(self, channels, q, skip_pooled, rows_of):
+        """clip / scale: per round one exact selection of the percentiles ``q``
+        (D.quantiles, one host read of its few numbers; ``skip_pooled``: the
+        pooled selection leaves out -99999) and one rescale pass.
+        ``rows_of(record)`` turns a channel's record into its D.rescale row and
+        whether the rescaled plane's range is known.  A channel listed twice
+        is processed twice, as the reference's loop does.
+
+        Raw pixels (or ones whose only pending state is earlier clip / scale
+        rounds) that are not resident, or whose fp32 result may not be held
+        (the HBM budget), keep the rounds deferred (``_pending_rescale``): the
+        selection reads the slide band by band (stream.quantiles) and every
+        pass that needs pixels rescales each band as it reads it
+        (stream.RescaleSource), before a later log_normalize or filter: the
+        resident bits.  With a log_normalize or a filter already pending the
+        pixels are materialised first (MemoryError when they do not fit); a
+        row band of a slide split over ranks is refused."""
+        from . import stream
+
         if getattr(self, "_band", None) is not None:
             raise NotImplementedError("clip / scale of a row band of a slide: the percentiles are the "
                                       "whole slide's")
-        t = self._materialize()  # a slide that is not resident: _device()'s MemoryError
-        C = int(t.shape[2])
-        for chs in self._channel_rounds(channels):
+        rounds = self._channel_rounds(channels)
+        deferred = False
+        rng = np.full((2, self.n_ch), np.nan)  # after a log_normalize or a filter: not known
+        if self._pending is None and not self._filter_deferred():
+            rng = self._range_now()
+            H, W = self.shape[0], self.shape[1]
+            deferred = self._source() is not None or not self._may_hold(H * W * self.n_ch * 4)
+        if deferred:
+            C = self.n_ch
+            base = self._raw_source()
+            if base is None:
+                base = stream.DeviceSource(self._device())
+            host, dev = ([], []) if self._pending_rescale is None else (list(x) for x in self._pending_rescale)
+        else:
+            t = self._materialize()  # a slide that is not resident: _device()'s MemoryError
+            C = int(t.shape[2])
+        lo, hi = rng[0].copy(), rng[1].copy()
+        for chs in rounds:
+            pooled = chs is None
             params = np.zeros((C, 5), dtype=np.float64)  # mode 0: the value itself
-            if chs is None:
-                params[:] = rows_of(D.d2h(select(t, True))[0])
+            if deferred:
+                rec = stream.quantiles(stream.RescaleSource(base, dev) if dev else base, q, pooled=pooled,
+                                       skip_sentinel=pooled and skip_pooled)
             else:
-                st = D.d2h(select(t, False))
-                for c in chs:
-                    params[c] = rows_of(st[c])
-            t = D.rescale(t, params)
-        self._set_device(t)
+                rec = D.quantiles(t, q, pooled=pooled, skip_sentinel=pooled and skip_pooled)
+            st = D.d2h(rec)
+            for c in range(C) if pooled else chs:
+                params[c], known = rows_of(st[0 if pooled else c])
+                lo[c], hi[c] = (params[c, 2], params[c, 3]) if known else (np.nan, np.nan)
+            if deferred:
+                host.append(params)
+                dev.append(D.h2d(params, D.device()))
+            else:
+                t = D.rescale(t, params)
+        if deferred:
+            self._pending_rescale = (host, dev)
+            self._host64 = None
+        else:
+            self._set_device(t)
+        self._range = np.stack([lo, hi])
         self._xbound = None
         self._lognorm_host = None
+
+    def _range_now(self):
+        """[2, n_ch] (lo, hi) of the current pixels, NaN where not known: what
+        earlier clip / scale rounds left, or a raw integer slide's type range."""
+        if self._range is not None:
+            return self._range
+        mx = self._raw_int_max()
+        if mx is None:
+            return np.full((2, self.n_ch), np.nan)
+        return np.stack([np.zeros(self.n_ch), np.full(self.n_ch, mx)])
 
     def clip(self, channels=None):
         """MxIF.py:330-343 / clip_values (MxIF.py:29-64): rescale to the 0.5 and
@@ -596,26 +698,31 @@ class img:
         out_range=np.float32) does.  ``channels`` None (or a 2-D image): one
         pair over all channels, elements equal to -99999 left out as well;
         else a tuple of channel indices (or names), each plane with its own
-        pair, the others unchanged.  The pixels become fp32."""
+        pair, the others unchanged.  The pixels become fp32.  A slide that is
+        not resident (or whose fp32 result may not be held) keeps the clip
+        deferred, see ``_intensity``; out of that scope, as before: a
+        log_normalize or a filter already pending materialises first, a row
+        band of a split slide raises."""
         def rows_of(st):
             n = int(st[0, 2])
-            return _clip_params(_lerp_quantile(st[0, 0], st[0, 1], n, _CLIP_Q[0]),
-                                _lerp_quantile(st[1, 0], st[1, 1], n, _CLIP_Q[1]))
+            row = _clip_params(_lerp_quantile(st[0, 0], st[0, 1], n, _CLIP_Q[0]),
+                               _lerp_quantile(st[1, 0], st[1, 1], n, _CLIP_Q[1]))
+            return row, n > 0 and st[0, 3] == 0  # (a NaN pixel stays NaN: no bound)
 
-        self._intensity(channels, lambda t, pooled: D.quantiles(t, _CLIP_Q, pooled=pooled,
-                                                                skip_sentinel=pooled), rows_of)
+        self._intensity(channels, _CLIP_Q, True, rows_of)
 
     def scale(self, channels=None):
         """MxIF.py:345-358 / scale_rgb (MxIF.py:67-92): (x - min) / (max - min),
         one min / max over everything (``channels`` None or a 2-D image) or per
         listed plane.  As numpy's min(): a plane holding a NaN becomes NaN, and
-        a constant plane gives 0/0 = NaN.  The pixels become fp32."""
+        a constant plane gives 0/0 = NaN.  The pixels become fp32.  Deferred
+        for a slide that is not resident, as ``clip``."""
         def rows_of(st):
             nan = float("nan")
             lo, hi = (st[0, 0], st[1, 1]) if st[0, 3] == 0 and st[0, 2] > 0 else (nan, nan)
-            return (lo, hi, 0.0, 1.0, D.RESCALE_SCALE)
+            return (lo, hi, 0.0, 1.0, D.RESCALE_SCALE), bool(hi > lo)  # (else the plane is NaN: no bound)
 
-        self._intensity(channels, lambda t, pooled: D.quantiles(t, (0.0, 100.0), pooled=pooled), rows_of)
+        self._intensity(channels, (0.0, 100.0), False, rows_of)
 
     def equalize_hist(self=None, channels=None, **kwargs):
         """MxIF.py:360-373 / CLAHE (MxIF.py:95-122): contrast-limited adaptive
@@ -626,7 +733,9 @@ class img:
         ``nbins`` (256, at most 256) as skimage's.  ``channels`` as ``clip``:
         None (or a 2-D image) means every plane, else indices or names, the
         other planes unchanged; a plane listed twice is equalised twice.  The
-        pixels become fp32."""
+        pixels become fp32.  The slide must be resident: deferred clip /
+        scale rounds are materialised first (MemoryError when that does not
+        fit); there is no banded form."""
         if "kernel_size" not in kwargs:  # also for the unbound call with no arguments at all
             raise _need_kernel_size("img.equalize_hist")
         kernel_size = kwargs.pop("kernel_size")
@@ -825,6 +934,8 @@ class img:
         are a raw uint8 / uint16 slide (device, host or streamed), else None."""
         if self._pending_blur is not None or self._pending_bilateral is not None:
             return None
+        if self._pending_rescale is not None:
+            return None
         if self._dev is not None:
             t = self._dev.dtype
         elif self._host is not None:
@@ -844,10 +955,15 @@ class img:
         take their fixed point from it (milwrm_amd.assign._DomainSSE): the
         label pass can then add each band's sums as it labels it, and the
         standalone estimators give the same bits without a first pass for the
-        column maxima.  None when the pixels are not such a slide."""
+        column maxima.  Clipped and scaled pixels are known as well, resident
+        or deferred (``_range``): a clipped channel lies in [0, 1] ([-1, 1] when
+        its lower percentile is negative), a scaled one in [0, 1], an untouched
+        one keeps its raw type's range; a log_normalize on top needs every
+        lower end >= 0.  None when the pixels are neither (a plane that scale
+        turned into NaN, a channel with NaN pixels, untouched fp32)."""
         mx = self._raw_int_max()
         if mx is None:
-            return None
+            return self._range_bound()
         if self._pending is None:
             return np.full(self.n_ch, mx * (1 + 1e-3))
         if self._lognorm_host is None:
@@ -858,6 +974,25 @@ class img:
         with np.errstate(invalid="ignore", over="ignore"):
             hi = np.log10(mx * inv.astype(np.float64) + p)
         return np.maximum(abs(np.log10(p)), np.abs(hi)) * (1 + 1e-3) + 1e-30
+
+    def _range_bound(self):
+        """``_blur_bound`` of clipped / scaled pixels (``_range``)."""
+        if self._range is None or self._pending_blur is not None or self._pending_bilateral is not None:
+            return None
+        lo, hi = self._range
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            return None
+        if self._pending is None:
+            return np.maximum(np.abs(lo), np.abs(hi)) * (1 + 1e-3)
+        if self._lognorm_host is None or (lo < 0).any():
+            return None
+        inv, p = self._lognorm_host
+        if not (np.isfinite(p) and p > 0):
+            return None
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            a = np.log10(lo * inv.astype(np.float64) + p)
+            b = np.log10(hi * inv.astype(np.float64) + p)
+        return np.maximum(np.abs(a), np.abs(b)) * (1 + 1e-3) + 1e-30
 
     def _blur_(self, sigma: float, truncate: float):
         """The gaussian branch of ``blurring``: deferred (streamed slide, or the
@@ -891,7 +1026,8 @@ class img:
     def log_normalize(self, pseudoval=1, mean=None, mask=True):
         """MxIF.py:416-455: log10(x/mean_c + pseudoval) on every pixel.  The
         transform is deferred and fused into the next blur (or materialised
-        when ``.img`` is read)."""
+        when ``.img`` is read).  Deferred clip / scale rounds stay deferred:
+        they apply before it."""
         if mask:
             assert self.mask is not None, "No tissue mask available"
         else:
@@ -909,7 +1045,8 @@ class img:
         with np.errstate(divide="ignore"):
             inv = (1.0 / mean).astype(np.float32)
         # a raw integer slide's bound survives a pending log_normalize (_blur_bound)
-        raw = self._raw_int_max() is not None and self._pending is None and self._pending_blur is None
+        raw = ((self._raw_int_max() is not None or self._range is not None) and self._pending is None
+               and self._pending_blur is None and self._pending_bilateral is None)
         self._pending = (D.h2d(inv, D.device()), float(pseudoval))
         self._lognorm_host = (inv, float(pseudoval)) if raw else None
         self._xbound = None
@@ -982,6 +1119,7 @@ class img:
                 filt = stream.LogNormBand(*self._pending)
             out = stream.downsample(src, fact, func, filt)
             self._pending = self._pending_blur = self._pending_median = self._pending_bilateral = None
+            self._pending_rescale = None
             self._lognorm_host = None
         else:
             out = D.block_reduce(self._materialize(), fact, func)

@@ -39,6 +39,10 @@ _PROTOS = {
     "mw_lognorm": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp]),
     "mw_quantiles_ws_bytes": (c_sz, [c_i32, c_i32]),
     "mw_quantiles": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "mw_quantiles_passes": (c_i32, [c_i32]),
+    "mw_quantiles_rows_begin": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mw_quantiles_rows_count": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mw_quantiles_rows_choose": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mw_rescale": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "mw_clahe_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "mw_clahe": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, C.c_double, c_i32, c_vp, c_vp, c_vp,

@@ -11,7 +11,9 @@
 // into global memory once per workgroup.  Between passes a one-workgroup
 // kernel picks, per channel and rank, the digit that holds the rank; ranks
 // come from the histogram's own sum, so nothing returns to the host before
-// the last pass has written the order statistics.
+// the last pass has written the order statistics.  A pass may be fed in pieces
+// (mw_quantiles_rows_*): the counts are integer adds into global memory, so
+// counting a slide band after band gives the whole slide's histograms.
 #include <math.h>
 
 #include "common.h"
@@ -89,10 +91,17 @@ struct SelState {
 // registers while a channel has at most kRegPrefixes of them (LREG; two
 // percentiles, as clip and scale ask), else in LDS beside the tables, where
 // the dependent LDS reads of every element bound the pass.
+//
+// A band of rows need not start on a 16-byte boundary: img is the band's start
+// rounded down to one, the band's elements are [off, n_elem) of it (off < V, so
+// only the first vector of workgroup 0 holds elements before the band: its
+// lane takes it element by element) and flat element e belongs to channel
+// (e + phase) % C, phase = (C - off % C) % C.
 template <typename T, bool FIRST, bool LREG>
 __global__ void __launch_bounds__(256) select_count_kernel(const T* __restrict__ img, int64_t n_elem,
                                                            int C, int L, int teff, int64_t epb,
-                                                           int shift, int skip, SelState st,
+                                                           int shift, int skip, int off, int phase,
+                                                           SelState st,
                                                            unsigned long long* __restrict__ hist) {
   constexpr int V = SelVec<T>::N;
   constexpr int S = FIRST ? kSlotsFirst : kSlotsNext;
@@ -114,7 +123,7 @@ __global__ void __launch_bounds__(256) select_count_kernel(const T* __restrict__
   uint32_t pr[LREG ? V : 1][kRegPrefixes];  // no prefix has its top byte set: ~0 matches none
 #pragma unroll
   for (int i = 0; i < V; ++i) {
-    chn[i] = (int)(((int64_t)t * V + i) % C);
+    chn[i] = (int)(((int64_t)t * V + i + phase) % C);
     nanc[i] = 0u;
     if constexpr (FIRST) {
       nu[i] = 1;
@@ -170,6 +179,12 @@ __global__ void __launch_bounds__(256) select_count_kernel(const T* __restrict__
     if (t < teff) {
       const int64_t stride = (int64_t)teff * V;
       int64_t e = lo + (int64_t)t * V;
+      if (off > 0 && e == 0) {  // the vector that straddles the band's start
+#pragma unroll
+        for (int i = 0; i < V; ++i)
+          if (i >= off && i < hi) take(img[i], i);
+        e += stride;
+      }
       // four independent 16-B loads in flight per iteration
       for (; e + 3 * stride + V <= hi; e += 4 * stride) {
         SelPack<T, V> p[4];
@@ -400,10 +415,7 @@ static SelLayout sel_layout(int C, int nq) {
   return o;
 }
 
-template <typename T>
-static int run_select(const void* d_img, int64_t n_elem, int Ce, int nq, int passes, int skip,
-                      const QList& qf, const SelLayout& lay, char* ws, double* d_out, hipStream_t s) {
-  const int L = 2 * nq;
+static SelState sel_state(const SelLayout& lay, char* ws) {
   SelState st;
   st.nan_cnt = reinterpret_cast<unsigned long long*>(ws + lay.nan_cnt);
   st.n_kept = reinterpret_cast<unsigned long long*>(ws + lay.n_kept);
@@ -414,27 +426,75 @@ static int run_select(const void* d_img, int64_t n_elem, int Ce, int nq, int pas
   st.slot_base = reinterpret_cast<int*>(ws + lay.slot_base);
   st.uprefix = reinterpret_cast<uint32_t*>(ws + lay.uprefix);
   st.n_slots = reinterpret_cast<int*>(ws + lay.n_slots);
+  return st;
+}
+
+static inline unsigned long long* sel_hist(const SelLayout& lay, char* ws, int Ce, int nq, int ps) {
+  return reinterpret_cast<unsigned long long*>(ws + lay.hist) + (size_t)ps * Ce * 2 * nq * 256;
+}
+
+static inline int sel_passes(int dtype) { return dtype == MW_U8 ? 1 : dtype == MW_U16 ? 2 : dtype == MW_F32 ? 4 : 0; }
+
+// Pass ps of the selection over the elements [off, n_elem) of the 16-byte
+// aligned img: added to the pass's histograms.
+template <typename T>
+static int run_count(const void* d_img, int64_t n_elem, int off, int Ce, int nq, int ps, int passes, int skip,
+                     const SelLayout& lay, char* ws, hipStream_t s) {
+  const int L = 2 * nq;
+  const SelState st = sel_state(lay, ws);
   const SelPlan p = sel_plan(n_elem, Ce, SelVec<T>::N, kSelBlocks);
   const T* img = reinterpret_cast<const T*>(d_img);
-  for (int ps = 0; ps < passes; ++ps) {
-    const int shift = 8 * (passes - 1 - ps);
-    unsigned long long* hist =
-        reinterpret_cast<unsigned long long*>(ws + lay.hist) + (size_t)ps * Ce * L * 256;
-    if (ps == 0)
-      hipLaunchKernelGGL((select_count_kernel<T, true, false>), dim3(p.G), dim3(256), 0, s, img, n_elem, Ce,
-                         L, p.teff, p.epb, shift, skip, st, hist);
-    else if (L <= kRegPrefixes)
-      hipLaunchKernelGGL((select_count_kernel<T, false, true>), dim3(p.G), dim3(256), 0, s, img, n_elem, Ce,
-                         L, p.teff, p.epb, shift, skip, st, hist);
-    else
-      hipLaunchKernelGGL((select_count_kernel<T, false, false>), dim3(p.G), dim3(256), 0, s, img, n_elem, Ce,
-                         L, p.teff, p.epb, shift, skip, st, hist);
-    MW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(select_choose_kernel<T>, dim3(1), dim3(kChoiceThreads), 0, s, Ce, nq,
-                       ps == 0 ? 1 : 0, ps == passes - 1 ? 1 : 0, qf, hist, st, d_out);
-    MW_LAUNCH_CHECK();
-  }
+  const int shift = 8 * (passes - 1 - ps);
+  const int phase = (Ce - off % Ce) % Ce;
+  unsigned long long* hist = sel_hist(lay, ws, Ce, nq, ps);
+  if (ps == 0)
+    hipLaunchKernelGGL((select_count_kernel<T, true, false>), dim3(p.G), dim3(256), 0, s, img, n_elem, Ce,
+                       L, p.teff, p.epb, shift, skip, off, phase, st, hist);
+  else if (L <= kRegPrefixes)
+    hipLaunchKernelGGL((select_count_kernel<T, false, true>), dim3(p.G), dim3(256), 0, s, img, n_elem, Ce,
+                       L, p.teff, p.epb, shift, skip, off, phase, st, hist);
+  else
+    hipLaunchKernelGGL((select_count_kernel<T, false, false>), dim3(p.G), dim3(256), 0, s, img, n_elem, Ce,
+                       L, p.teff, p.epb, shift, skip, off, phase, st, hist);
+  MW_LAUNCH_CHECK();
   return MW_OK;
+}
+
+template <typename T>
+static int run_choose(int Ce, int nq, int ps, int passes, const QList& qf, const SelLayout& lay, char* ws,
+                      double* d_out, hipStream_t s) {
+  hipLaunchKernelGGL(select_choose_kernel<T>, dim3(1), dim3(kChoiceThreads), 0, s, Ce, nq, ps == 0 ? 1 : 0,
+                     ps == passes - 1 ? 1 : 0, qf, sel_hist(lay, ws, Ce, nq, ps), sel_state(lay, ws), d_out);
+  MW_LAUNCH_CHECK();
+  return MW_OK;
+}
+
+static int sel_count(const void* d_img, int dtype, int64_t n_elem, int off, int Ce, int nq, int ps, int skip,
+                     const SelLayout& lay, char* ws, hipStream_t s) {
+  switch (dtype) {
+    case MW_U8: return run_count<uint8_t>(d_img, n_elem, off, Ce, nq, ps, 1, 0, lay, ws, s);
+    case MW_U16: return run_count<uint16_t>(d_img, n_elem, off, Ce, nq, ps, 2, 0, lay, ws, s);
+    default: return run_count<float>(d_img, n_elem, off, Ce, nq, ps, 4, skip, lay, ws, s);
+  }
+}
+
+static int sel_choose(int dtype, int Ce, int nq, int ps, const QList& qf, const SelLayout& lay, char* ws,
+                      double* d_out, hipStream_t s) {
+  switch (dtype) {
+    case MW_U8: return run_choose<uint8_t>(Ce, nq, ps, 1, qf, lay, ws, d_out, s);
+    case MW_U16: return run_choose<uint16_t>(Ce, nq, ps, 2, qf, lay, ws, d_out, s);
+    default: return run_choose<float>(Ce, nq, ps, 4, qf, lay, ws, d_out, s);
+  }
+}
+
+// the percentiles as fractions; false: one lies outside [0, 100]
+static bool sel_qlist(const double* h_q, int nq, QList& qf, int& bad) {
+  for (int i = 0; i < kMaxQ; ++i) qf.q[i] = 0.0;
+  for (int i = 0; i < nq; ++i) {
+    if (!(h_q[i] >= 0.0 && h_q[i] <= 100.0)) { bad = i; return false; }
+    qf.q[i] = h_q[i] / 100.0;
+  }
+  return true;
 }
 
 }  // namespace mw
@@ -457,11 +517,8 @@ int mw_quantiles(const void* d_img, int dtype, int64_t n_pix, int C, int pooled,
   MW_CHECK_ARG(((uintptr_t)d_img & 15) == 0 && ((uintptr_t)d_ws & 15) == 0,
                "mw_quantiles: image and workspace must be 16-byte aligned");
   QList qf;
-  for (int i = 0; i < kMaxQ; ++i) qf.q[i] = 0.0;
-  for (int i = 0; i < nq; ++i) {
-    MW_CHECK_ARG(h_q[i] >= 0.0 && h_q[i] <= 100.0, "mw_quantiles: q[%d]=%g outside [0, 100]", i, h_q[i]);
-    qf.q[i] = h_q[i] / 100.0;
-  }
+  int bad = 0;
+  MW_CHECK_ARG(sel_qlist(h_q, nq, qf, bad), "mw_quantiles: q[%d]=%g outside [0, 100]", bad, h_q[bad]);
   MW_CHECK_ARG(dtype == MW_U8 || dtype == MW_U16 || dtype == MW_F32, "mw_quantiles: bad dtype %d", dtype);
   const int Ce = pooled ? 1 : C;
   if (Ce > kMaxSelC) {
@@ -474,11 +531,79 @@ int mw_quantiles(const void* d_img, int dtype, int64_t n_pix, int C, int pooled,
   MW_HIP(hipMemsetAsync(d_ws, 0, lay.total, s));
   const int64_t n_elem = n_pix * C;
   char* ws = reinterpret_cast<char*>(d_ws);
-  switch (dtype) {
-    case MW_U8: return run_select<uint8_t>(d_img, n_elem, Ce, nq, 1, 0, qf, lay, ws, d_out, s);
-    case MW_U16: return run_select<uint16_t>(d_img, n_elem, Ce, nq, 2, 0, qf, lay, ws, d_out, s);
-    default: return run_select<float>(d_img, n_elem, Ce, nq, 4, skip_sentinel, qf, lay, ws, d_out, s);
+  const int passes = sel_passes(dtype);
+  for (int ps = 0; ps < passes; ++ps) {
+    int rc = sel_count(d_img, dtype, n_elem, 0, Ce, nq, ps, skip_sentinel, lay, ws, s);
+    if (rc != MW_OK) return rc;
+    rc = sel_choose(dtype, Ce, nq, ps, qf, lay, ws, d_out, s);
+    if (rc != MW_OK) return rc;
   }
+  return MW_OK;
+}
+
+int mw_quantiles_passes(int dtype) { return sel_passes(dtype); }
+
+int mw_quantiles_rows_begin(int C, int pooled, int nq, void* d_ws, void* stream) {
+  MW_CHECK_ARG(d_ws, "mw_quantiles_rows_begin: null pointer");
+  MW_CHECK_ARG(C >= 1, "mw_quantiles_rows_begin: bad shape C=%d", C);
+  MW_CHECK_ARG(nq >= 1 && nq <= kMaxQ, "mw_quantiles_rows_begin: nq=%d outside 1..%d", nq, kMaxQ);
+  MW_CHECK_ARG(((uintptr_t)d_ws & 15) == 0, "mw_quantiles_rows_begin: the workspace must be 16-byte aligned");
+  const int Ce = pooled ? 1 : C;
+  if (Ce > kMaxSelC) {
+    set_error("mw_quantiles_rows_begin: %d channels (per-channel selection takes up to %d)", C, kMaxSelC);
+    return MW_EUNSUPPORTED;
+  }
+  MW_HIP(hipMemsetAsync(d_ws, 0, sel_layout(Ce, nq).total, as_stream(stream)));
+  return MW_OK;
+}
+
+int mw_quantiles_rows_count(const void* d_rows, int dtype, int64_t n_pix, int C, int pooled, int nq,
+                            int skip_sentinel, int pass, void* d_ws, void* stream) {
+  MW_CHECK_ARG(d_rows && d_ws, "mw_quantiles_rows_count: null pointer");
+  MW_CHECK_ARG(C >= 1 && n_pix >= 1, "mw_quantiles_rows_count: bad shape n_pix=%lld C=%d", (long long)n_pix, C);
+  MW_CHECK_ARG(n_pix <= ((int64_t)1 << 40) / C, "mw_quantiles_rows_count: more than 2^40 elements");
+  MW_CHECK_ARG(nq >= 1 && nq <= kMaxQ, "mw_quantiles_rows_count: nq=%d outside 1..%d", nq, kMaxQ);
+  MW_CHECK_ARG(dtype == MW_U8 || dtype == MW_U16 || dtype == MW_F32, "mw_quantiles_rows_count: bad dtype %d",
+               dtype);
+  MW_CHECK_ARG(pass >= 0 && pass < sel_passes(dtype), "mw_quantiles_rows_count: pass %d outside 0..%d", pass,
+               sel_passes(dtype) - 1);
+  const uintptr_t p = (uintptr_t)d_rows;
+  const int elem = dtype == MW_U8 ? 1 : dtype == MW_U16 ? 2 : 4;
+  MW_CHECK_ARG(p % elem == 0 && ((uintptr_t)d_ws & 15) == 0,
+               "mw_quantiles_rows_count: rows must be element aligned, the workspace 16-byte aligned");
+  const int Ce = pooled ? 1 : C;
+  if (Ce > kMaxSelC) {
+    set_error("mw_quantiles_rows_count: %d channels (per-channel selection takes up to %d)", C, kMaxSelC);
+    return MW_EUNSUPPORTED;
+  }
+  // the band from the 16-byte boundary at or below its start: the elements
+  // before it are loaded with the first vector and left out
+  const int off = (int)((p & 15) / elem);
+  const void* base = reinterpret_cast<const void*>(p & ~(uintptr_t)15);
+  return sel_count(base, dtype, n_pix * C + off, off, Ce, nq, pass, skip_sentinel, sel_layout(Ce, nq),
+                   reinterpret_cast<char*>(d_ws), as_stream(stream));
+}
+
+int mw_quantiles_rows_choose(int dtype, int C, int pooled, const double* h_q, int nq, int pass, double* d_out,
+                             void* d_ws, void* stream) {
+  MW_CHECK_ARG(h_q && d_out && d_ws, "mw_quantiles_rows_choose: null pointer");
+  MW_CHECK_ARG(C >= 1, "mw_quantiles_rows_choose: bad shape C=%d", C);
+  MW_CHECK_ARG(nq >= 1 && nq <= kMaxQ, "mw_quantiles_rows_choose: nq=%d outside 1..%d", nq, kMaxQ);
+  MW_CHECK_ARG(dtype == MW_U8 || dtype == MW_U16 || dtype == MW_F32, "mw_quantiles_rows_choose: bad dtype %d",
+               dtype);
+  MW_CHECK_ARG(pass >= 0 && pass < sel_passes(dtype), "mw_quantiles_rows_choose: pass %d outside 0..%d", pass,
+               sel_passes(dtype) - 1);
+  MW_CHECK_ARG(((uintptr_t)d_ws & 15) == 0, "mw_quantiles_rows_choose: the workspace must be 16-byte aligned");
+  QList qf;
+  int bad = 0;
+  MW_CHECK_ARG(sel_qlist(h_q, nq, qf, bad), "mw_quantiles_rows_choose: q[%d]=%g outside [0, 100]", bad, h_q[bad]);
+  const int Ce = pooled ? 1 : C;
+  if (Ce > kMaxSelC) {
+    set_error("mw_quantiles_rows_choose: %d channels (per-channel selection takes up to %d)", C, kMaxSelC);
+    return MW_EUNSUPPORTED;
+  }
+  return sel_choose(dtype, Ce, nq, pass, qf, sel_layout(Ce, nq), reinterpret_cast<char*>(d_ws), d_out,
+                    as_stream(stream));
 }
 
 int mw_rescale(const void* d_img, int dtype, int64_t n_pix, int C, const double* d_params, float* d_out,

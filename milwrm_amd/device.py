@@ -298,6 +298,60 @@ def quantiles(img: torch.Tensor, q, pooled: bool = False, skip_sentinel: bool = 
     return out
 
 
+class RowQuantiles:
+    """``quantiles`` of a slide that is handed over in bands of rows
+    (mw_quantiles_rows_*; stream.quantiles): per pass ``count`` every band,
+    then ``choose``; after the last pass ``out`` is the record ``quantiles``
+    gives for the whole slide, bit for bit, whatever the bands.  A band is a
+    contiguous [rows, W, C] tensor of the slide's element type that may start
+    anywhere (a view into a resident slide: no 16-byte alignment is asked).
+    Nothing is synchronised."""
+
+    def __init__(self, dtype, C: int, q, pooled: bool = False, skip_sentinel: bool = False, dev=None):
+        try:
+            self.code = _DTYPE_CODE[dtype]
+        except KeyError:
+            raise TypeError(f"unsupported device image dtype {dtype}") from None
+        self.dtype, self.C = dtype, int(C)
+        self.qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        self.nq = int(self.qa.size)
+        if not ((self.qa >= 0) & (self.qa <= 100)).all():  # (NaN too) before the first launch
+            raise ValueError(f"quantiles: percentiles {self.qa.tolist()} outside [0, 100]")
+        self.pooled, self.skip = int(bool(pooled)), int(bool(skip_sentinel))
+        self.passes = N.query("mw_quantiles_passes", self.code)
+        self.elem = torch.empty(0, dtype=dtype).element_size()
+        self.ps = 0
+        dev = device() if dev is None else dev
+        self.ws = WS.get("quantiles", N.query("mw_quantiles_ws_bytes", self.C, max(1, min(self.nq, 8))))
+        N.call("mw_quantiles_rows_begin", self.C, self.pooled, self.nq, P(self.ws), stream())
+        self.out = torch.empty((1 if pooled else self.C, self.nq, 4), dtype=torch.float64, device=dev)
+
+    def count(self, rows: torch.Tensor):
+        """Add a band to the current pass (every band once in every pass)."""
+        if rows.dtype != self.dtype or rows.dim() != 3 or int(rows.shape[2]) != self.C:
+            raise ValueError(f"quantiles: a band must be [rows, W, {self.C}] of {self.dtype}, got "
+                             f"{tuple(rows.shape)} of {rows.dtype}")
+        if not rows.is_contiguous():
+            raise ValueError("quantiles: the band must be contiguous")
+        if self.ps >= self.passes:
+            raise ValueError("quantiles: every pass of this selection has been chosen")
+        n_pix = int(rows.shape[0]) * int(rows.shape[1])
+        if n_pix == 0:
+            return
+        with profiling.timed("quantiles", n_pix * self.C * self.elem):
+            N.call("mw_quantiles_rows_count", P(rows), self.code, n_pix, self.C, self.pooled, self.nq, self.skip,
+                   self.ps, P(self.ws), stream())
+
+    def choose(self) -> bool:
+        """End the current pass after its last band; True once ``out`` is written."""
+        if self.ps >= self.passes:
+            raise ValueError("quantiles: every pass of this selection has been chosen")
+        N.call("mw_quantiles_rows_choose", self.code, self.C, self.pooled, self.qa.ctypes.data, self.nq, self.ps,
+               P(self.out), P(self.ws), stream())
+        self.ps += 1
+        return self.ps == self.passes
+
+
 RESCALE_PASS, RESCALE_CLIP, RESCALE_FLAT, RESCALE_SCALE = 0.0, 1.0, 2.0, 3.0
 
 
@@ -822,6 +876,8 @@ FUSED_USED = {"sample": 0, "assign": 0, "assign_banded": 0, "sample_streamed": 0
 # median paths taken (tests read it): the register selection network or the generic rank search;
 # rows_streamed: bands filtered from a slide that is not resident (stream.MedianBand)
 MEDIAN_USED = {"network": 0, "generic": 0, "rows_streamed": 0}
+# selections fed band by band from a slide that is not resident; bands rescaled on their way in
+INTENSITY_USED = {"select_streamed": 0, "rescale_streamed": 0}
 # bands of a slide that is not resident filtered by the deferred bilateral (stream.BilateralBand)
 BILATERAL_USED = {"rows_streamed": 0}
 

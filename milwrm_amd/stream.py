@@ -32,7 +32,12 @@ Here:
   visits a pixel's taps in one order whichever tile or band computes it
   (mw_bilateral_rows), and the whole-slide numbers it needs come from
   ``image_moments``, whose bits do not depend on the bands
-  (tests/test_gpu_bilateral_stream.py).
+  (tests/test_gpu_bilateral_stream.py);
+* ``img.clip`` / ``img.scale`` of a slide that is not resident select their
+  percentiles band by band (``quantiles``: integer histograms, the whole
+  slide's bits) and stay deferred as a ``RescaleSource``: a source that wraps
+  the raw one and hands every band on rescaled, so every pass above takes it
+  unchanged (tests/test_gpu_intensity_stream.py).
 
 Sources (``RowSource``): ``DeviceSource`` (a resident tensor; its bands are
 views, no copy), ``HostSource`` (a host array: pinned memory -- e.g.
@@ -301,6 +306,51 @@ class HostSource(RowSource):
         return dst
 
 
+class RescaleSource(RowSource):
+    """A slide seen through deferred ``img.clip`` / ``img.scale`` rounds:
+    ``inner``'s rows through ``device.rescale`` (mw_rescale: the fp64,
+    contraction-free expression, rounded once), one table after the other, as
+    fp32.  The band is read into a staging buffer of the inner element type
+    (an fp32 band straight into ``out``, a resident slide's band is its view)
+    and rescaled into ``out`` on the stream the read is enqueued on, so
+    ``bands`` prefetches and rescales band b+1 beside the work on band b.
+    Every band pass that takes a source takes this one: the rescale is an
+    elementwise pass of its own, before any log_normalize or filter of the
+    pass, and is done again by every pass.  ``tables``: device fp64 [C, 5]."""
+
+    kind = "rescale"
+
+    def __init__(self, inner, tables):
+        self.inner = as_source(inner)
+        self.H, self.W, self.C = self.inner.H, self.inner.W, self.inner.C
+        self.dtype = torch.float32
+        self.tables = list(tables)
+        assert self.tables, "RescaleSource: no rescale table"
+
+    def read(self, y0, y1, out):
+        inner = self.inner
+        dst = out[:y1 - y0]
+        if inner.zero_copy:
+            raw = inner.read(y0, y1, None)
+            if raw.data_ptr() % 16 or not raw.is_contiguous():  # mw_rescale loads 16-byte vectors
+                raw = raw.clone(memory_format=torch.contiguous_format)
+        elif inner.dtype == torch.float32:
+            raw = inner.read(y0, y1, dst)  # rescaled in place
+        else:
+            # (allocated and released on the reading stream: the allocator hands the
+            # block to the next band's read on that stream, after this band's rescale)
+            raw = inner.read(y0, y1, alloc_rows(y1 - y0, (self.W, self.C), inner.dtype, min_rows=y1 - y0,
+                                                dev=out.device))
+        for i, tab in enumerate(self.tables):
+            D.rescale(raw if i == 0 else dst, tab, out=dst)
+        if not inner.zero_copy:
+            D.INTENSITY_USED["rescale_streamed"] += 1
+        return dst
+
+    def mask_device(self):
+        return self.inner.mask_device()
+
+
 def pinned_empty(shape, dtype=torch.int16) -> torch.Tensor:
     """Page-locked host tensor: bands of a HostSource over it are copied by
     DMA without a staging copy."""
@@ -510,6 +560,27 @@ def nz_stats(src: RowSource):
         s += sb
         c += cb
     return s, c
+
+
+def quantiles(src, q, pooled: bool = False, skip_sentinel: bool = False, band_rows=None) -> torch.Tensor:
+    """``device.quantiles`` of a slide band after band (``img.clip`` /
+    ``img.scale`` of a slide that is not resident): passes x bands through
+    mw_quantiles_rows_*, no halo, any band height.  The histograms are integer
+    sums, so the record is the whole slide's, bit for bit.  The source is read
+    once per pass: once for uint8, twice for uint16, four times for fp32 (a
+    ``RescaleSource`` included, whose rescale runs again with every read).
+    Nothing is synchronised: the caller reads the few numbers."""
+    src = as_source(src)
+    sel = D.RowQuantiles(src.dtype, src.C, q, pooled, skip_sentinel)
+    if band_rows is None:
+        band_rows = src.H if src.zero_copy else band_rows_for(src)
+    for _ in range(sel.passes):
+        for _, _, _, raw in bands(src, band_rows, 0):
+            sel.count(raw)
+        sel.choose()
+    if not src.zero_copy:
+        D.INTENSITY_USED["select_streamed"] += 1
+    return sel.out
 
 
 class GaussianBand:
@@ -732,7 +803,8 @@ def blur_gather(src, sigma: float, inv_mean, pseudoval: float, feat: torch.Tenso
                               y0 - a, y1 - a, D.P(inv_mean), float(pseudoval), w.ctypes.data, r, D.P(slots), S,
                               D.P(feat), F, D.P(X_out), D.stream())
 
-    return _band_gather(src, filt, feat, idx, r2p, X_out, band_rows, fused)
+    # (the fused kernel's load is the log_normalize: a blur of pixels as they are takes the band path)
+    return _band_gather(src, filt, feat, idx, r2p, X_out, band_rows, fused if inv_mean is not None else None)
 
 
 def median_gather(src, size, inv_mean, pseudoval: float, feat: torch.Tensor, idx: torch.Tensor, r2p,
