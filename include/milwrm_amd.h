@@ -285,6 +285,26 @@ int mw_blur(const void* d_img, int dtype, int H, int W, int C,
             const float* d_inv_mean, float pseudoval,
             const float* h_w, int radius, float* d_out, void* d_ws, void* stream);
 
+/* The blur in two parts: first the rows the labelling path can read, the rest
+ * only if something else reads the image (no reference counterpart).  A pixel
+ * is needed when its 64-aligned flat tile (p >> 6, p = y W + x) holds a mask
+ * pixel: the tiles mw_assign_conf loads, which cover the pixels a gather over
+ * the mask reads.  mw_blur_rows_table writes, per workgroup tile of the
+ * matrix-core kernel (mw_blur_rows_tiles(H, W) of them, 64 columns x 512 rows,
+ * column band fastest), the hull [a, b) of its output rows that hold a needed
+ * pixel into d_table[2 t], d_table[2 t + 1] (a = b: none); d_mask is H x W
+ * bytes, nonzero = tissue.  mw_blur_part blurs, with mw_blur's arguments, the
+ * rows of the hulls (part 1) or the rows outside them (part 2) and leaves the
+ * other rows of d_out untouched: part 1 then part 2 write mw_blur's d_out, bit
+ * for bit.  MW_EUNSUPPORTED, nothing launched, for shapes the matrix-core
+ * kernel does not take (odd C, C > 64, radius > 8, MW_BLUR_IMPL=v): those are
+ * blurred whole by mw_blur.  The table stays on the device. */
+int mw_blur_rows_tiles(int H, int W);
+int mw_blur_rows_table(const uint8_t* d_mask, int H, int W, int32_t* d_table, void* stream);
+int mw_blur_part(const void* d_img, int dtype, int H, int W, int C,
+                 const float* d_inv_mean, float pseudoval, const float* h_w, int radius,
+                 float* d_out, const int32_t* d_table, int part, void* stream);
+
 /* ---- img.downsample(fact, np.mean) (MxIF.py:494-517) ------------------------
  * block mean over fact x fact, zero padded to a multiple of fact, pad zeros
  * included.  HWC in, fp32 HWC out of ceil(H/f) x ceil(W/f) x C. */
@@ -498,7 +518,7 @@ int mw_kpp_step(const float* d_X, int64_t S, int F, const double* d_mu,
 int mw_kpp_indices(const void* d_ws, int64_t S, int T, int k, int64_t* d_idx_out,
                    void* stream);
 /* single-device last step (c = k-1 >= 2, mw_kpp_fold_supported) with the
- * first Lloyd E-step folded into its pass (the fit driver's default; no
+ * first Lloyd E-step folded into its pass (opt-in: MW_KPP_FOLD=1; no
  * reference counterpart: it replaces the pass over the rows that sklearn's
  * first lloyd_iter_chunked_dense makes after _kmeans_plusplus, _kmeans.py:
  * 624-752): besides the step's trial sums, every row gets its label among the
@@ -517,7 +537,7 @@ int mw_kpp_step_fold(const float* d_X, int64_t S, int F, const double* d_mu, con
                      uint8_t* d_moved, void* d_centers_img, double* d_rec, double* d_rec_out, void* stream);
 size_t mw_kpp_fold_rec_bytes(int64_t S, int k, int F);
 /* 1 when mw_kpp_step_fold takes (k, F, T): 3 <= k <= 16, T <= 4, F <= 32 and
- * its LDS fits four blocks per CU */
+ * its LDS fits two blocks per CU */
 int mw_kpp_fold_supported(int k, int F, int T);
 /* device address of the k-means++ workspace's selected-array index (int) */
 const int* mw_kpp_best_ptr(const void* d_ws, int64_t S, int T);

@@ -296,7 +296,11 @@ def _assign_img_(image: img, features, centers, scaler, qc):
                                   centers, image._mask_device(), qc=q)
         if res is not None:
             return out(res)
-    src = D.as_float32(image._materialize())
+    # assign_image loads only the 64-pixel tiles that hold a mask pixel: a partly blurred
+    # image (img._blur_rest) stays so, unless the QC sums read the whole slide in the same pass.
+    # (A row band of a slide is never partly blurred -- img._blur_ blurs it whole, its gather
+    # reads whole images -- so the per-band form below has nothing to leave pending.)
+    src = image._needed_pixels() if q is None and band is None else D.as_float32(image._materialize())
     if band is not None:  # label the band rows only (milwrm_amd.bands)
         return out(assign_image(src[band.rows], feats, mu, inv, centers,
                                 D.padded_mask(image._mask_device()[band.rows].contiguous())))
@@ -677,7 +681,7 @@ class mxif_labeler(tissue_labeler):
                     rec = D.col_stats_rows(X[off:off + S], img_stats[n_img], accumulate=False,
                                            absmax=xmax, keep_records=True)
                 else:
-                    rec = D.gather_rows(D.as_float32(im._materialize()), feat, idx, None if px else r2p,
+                    rec = D.gather_rows(im._needed_pixels(), feat, idx, None if px else r2p,
                                         X[off:off + S], img_stats[n_img], accumulate=False, absmax=xmax,
                                         keep_records=True)
                 moments.append((off, S) + rec)

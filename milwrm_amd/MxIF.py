@@ -110,6 +110,62 @@ class _DeviceMask:
 
 
 class img:
+    # A gaussian blur of a resident slide with a mask writes, at first, only the
+    # rows the labelling path can read (D.blur_needed): _dev_t is
+    # then partly written and _blur_rest holds the completion's arguments.
+    # Every read of ``_dev`` completes the image first (_finish_blur); only the
+    # subsample gather and the label pass go round it (_needed_pixels).  The
+    # rows written are those the mask needed when the blur ran: assigning
+    # ``mask`` completes the image, but a mask array or device tensor changed
+    # IN PLACE while a rest is pending is not seen -- complete first
+    # (``_finish_blur()``, or read ``img``) before editing a mask in place.
+    _dev_t = None
+    _blur_rest = None
+
+    @property
+    def _dev(self):
+        if self._blur_rest is not None:
+            self._finish_blur()
+        return self._dev_t
+
+    @_dev.setter
+    def _dev(self, t):
+        self._blur_rest = None  # (new pixels: nothing of the old ones is left to finish)
+        self._dev_t = t
+
+    def _finish_blur(self):
+        """Blur the rows a partial gaussian left out (once; D.blur_rest)."""
+        rest, self._blur_rest = self._blur_rest, None
+        if rest is not None:
+            D.blur_rest(self._dev_t, rest)
+            self._count_resident()  # the raw slide is let go
+
+    def _count_resident(self):
+        """The HBM budget's count of an evictable transformed copy: its own
+        bytes and, while a rest is pending, the raw slide the rest keeps."""
+        from .stream import RESIDENCY
+
+        if self._revert is None or self._dev_t is None:
+            return
+        n = self._dev_t.numel() * self._dev_t.element_size()
+        if self._blur_rest is not None:
+            raw = self._blur_rest[0]
+            n += raw.numel() * raw.element_size()
+        RESIDENCY.register(self, n)
+
+    def _needed_pixels(self) -> torch.Tensor:
+        """The fp32 pixels for a reader that looks only at pixels whose
+        64-aligned flat tile holds a mask pixel (the subsample gather, the
+        label pass): a partly blurred image stays so.  Anything pending on top
+        of it applies to whole images and completes it first."""
+        from .stream import RESIDENCY
+
+        if (self._blur_rest is not None and self._pending is None and self._pending_rescale is None
+                and not self._filter_deferred()):
+            RESIDENCY.touch(self)
+            return self._dev_t
+        return D.as_float32(self._materialize())
+
     def __init__(self, img_arr, channels=None, mask=None):
         """Same validation and attributes as MxIF.py:126-167 (``img``, ``n_ch``,
         ``ch``, ``mask``); the pixels are uploaded lazily."""
@@ -153,8 +209,8 @@ class img:
     # every pass that needs them streams them in row bands (milwrm_amd.stream)
     @property
     def shape(self):
-        if self._dev is not None:
-            return tuple(self._dev.shape) if self._ndim > 2 else tuple(self._dev.shape[:2])
+        if self._dev_t is not None:
+            return tuple(self._dev_t.shape) if self._ndim > 2 else tuple(self._dev_t.shape[:2])
         if self._host is None and self._src is not None:
             return self._src.shape if self._ndim > 2 else self._src.shape[:2]
         return self._host.shape
@@ -175,8 +231,8 @@ class img:
 
         if self._pending_rescale is not None:
             return 4
-        if self._dev is not None:
-            return self._dev.element_size()
+        if self._dev_t is not None:
+            return self._dev_t.element_size()
         t = self._src.dtype if self._host is None else device_dtype_of(self._host)
         return torch.empty(0, dtype=t).element_size()
 
@@ -237,7 +293,7 @@ class img:
         """``_source`` of the raw pixels (before any deferred clip / scale)."""
         from .stream import RESIDENCY, HostSource
 
-        if self._dev is not None:
+        if self._dev_t is not None:
             RESIDENCY.touch(self)
             return None
         if self._band is not None:  # a slide band (milwrm_amd.bands) stays resident
@@ -451,6 +507,7 @@ class img:
 
     @mask.setter
     def mask(self, m):
+        self._finish_blur()  # (a partly blurred image holds the rows the old mask needs)
         self._mask = m
         self._mask_dev = None
         self._mrank = None
@@ -520,7 +577,10 @@ class img:
     @classmethod
     def from_device(cls, tensor, mask=None, channels=None) -> "img":
         """Wrap an HWC image already resident in HBM (uint8 / uint16-as-int16 /
-        fp32) and an optional device mask (nonzero = tissue)."""
+        fp32) and an optional device mask (nonzero = tissue).  The mask tensor
+        is kept by reference: it must not be changed in place between a
+        gaussian ``blurring`` and the passes that follow it (the blur writes
+        the rows that mask needs first)."""
         assert tensor.dim() == 3, "device image must be H x W x C"
         obj = cls.__new__(cls)
         obj._ndim = 3
@@ -764,6 +824,7 @@ class img:
         if filter_name == "gaussian":
             print("Applying gaussian filter")
             truncate = float(kwargs.pop("truncate", 4.0))
+            eager = bool(kwargs.pop("_eager", False))  # private: blur every row now (tests)
             mode = kwargs.pop("mode", "nearest")
             kwargs.pop("preserve_range", None)
             if mode != "nearest" or kwargs:
@@ -772,7 +833,7 @@ class img:
             if self._pending_median is not None or self._pending_bilateral is not None:
                 self._materialize()  # a second filter: the deferred one applies first
             bound = self._blur_bound()
-            self._blur_(float(sigma), truncate)
+            self._blur_(float(sigma), truncate, eager)
             self._xbound = bound
         elif filter_name == "median" and "size" in kwargs:
             # what the reference's branch evidently means: skimage's
@@ -936,8 +997,8 @@ class img:
             return None
         if self._pending_rescale is not None:
             return None
-        if self._dev is not None:
-            t = self._dev.dtype
+        if self._dev_t is not None:
+            t = self._dev_t.dtype
         elif self._host is not None:
             t = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.int16}.get(self._host.dtype)
         elif self._src is not None:
@@ -994,9 +1055,11 @@ class img:
             b = np.log10(hi * inv.astype(np.float64) + p)
         return np.maximum(np.abs(a), np.abs(b)) * (1 + 1e-3) + 1e-30
 
-    def _blur_(self, sigma: float, truncate: float):
+    def _blur_(self, sigma: float, truncate: float, eager: bool = False):
         """The gaussian branch of ``blurring``: deferred (streamed slide, or the
-        fp32 copy would not fit) or materialised."""
+        fp32 copy would not fit) or materialised.  A materialised blur of a
+        whole slide with a mask writes only the rows the labelling path can
+        read and leaves the rest pending (``_blur_rest``) unless ``eager``."""
         if self._pending_median is not None or self._pending_bilateral is not None:
             self._materialize()  # a second filter: the deferred one applies first
         if self._pending_blur is None and self._source() is not None:
@@ -1020,8 +1083,22 @@ class img:
         if self._pending is None:
             self._pending = (None, 1.0)
         inv, p = self._pending
-        self._transformed(lambda: D.blur(src, sigma, inv_mean=inv, pseudoval=p,
-                                         truncate=truncate))
+        # the pending rest keeps the raw slide next to the fp32 one: only within the budget
+        # (a row band of a slide gathers through whole-image reads: blurred whole)
+        partial = (not eager and self._mask is not None and src.dim() == 3 and self._band is None
+                   and self._may_hold(src.numel() * (4 + src.element_size())))
+        rest = []
+
+        def make():
+            if not partial:
+                return D.blur(src, sigma, inv_mean=inv, pseudoval=p, truncate=truncate)
+            out, r = D.blur_needed(src, sigma, self._mask_device(), inv_mean=inv, pseudoval=p, truncate=truncate)
+            rest.append(r)
+            return out
+
+        self._transformed(make)
+        self._blur_rest = rest[0] if rest else None
+        self._count_resident()
 
     def log_normalize(self, pseudoval=1, mean=None, mask=True):
         """MxIF.py:416-455: log10(x/mean_c + pseudoval) on every pixel.  The
@@ -1061,7 +1138,7 @@ class img:
         features = self._features(features)
         np.random.seed(random_state)  # the reference's global-RNG side effect (MxIF.py:484)
         deferred = self._filter_deferred()
-        src = None if deferred else D.as_float32(self._materialize())
+        src = None if deferred else self._needed_pixels()  # gather_rows reads mask pixels only
         r2p, M = self._mask_rank()
         dev = D.device()
         d_idx, total = subsample_indices_device(M, fract, random_state, dev)

@@ -64,6 +64,9 @@ _PROTOS = {
     "mw_image_moments": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp]),
     "mw_blur_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "mw_blur": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "mw_blur_rows_tiles": (c_i32, [c_i32, c_i32]),
+    "mw_blur_rows_table": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "mw_blur_part": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mw_block_mean": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mw_block_reduce_rows": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mw_mask_rank_ws_bytes": (c_sz, [c_i64]),

@@ -198,9 +198,17 @@ constexpr float kH16XS = 256.f, kH16TS = 65536.f, kH16VS = 1.f / 16777216.f;
 // dealing adjacent bands to one XCD (xcd = 1: block b takes logical tile
 // (b % 8) * (tiles / 8) + b / 8) slower.  MW_BLUR_BH and MW_BLUR_XCD override
 // both for tuning.
+// Row-range table (kEpiStore only, mw_blur_rows_table): per tile by * nbx + bx
+// the hull [a, b) of its output rows that hold a needed pixel (a = b = the
+// band's first row: none).  part kBlurNeeded blurs the hulls, one workgroup
+// per tile; part kBlurRest their complement, two workgroups per tile (blocks
+// [0, ntiles): the band's rows above a, blocks [ntiles, 2 ntiles): from b on).
+constexpr int kBlurWhole = 0, kBlurNeeded = 1, kBlurRest = 2;
 struct BlurGrid {
   int bh, nbx, ntiles, xcd;
   int r0, r1;  // output rows [r0, r1) of the input array (the whole array but for streamed bands)
+  const int* rows;  // row-range table (null: every tile blurs its whole band)
+  int part;
   __device__ __forceinline__ void tile(int b, int G, int& bx, int& by) const {
     const int x = b & 7, j = b >> 3, q = G >> 3, rem = G & 7;
     const int t = xcd ? x * q + (x < rem ? x : rem) + j : b;
@@ -216,6 +224,8 @@ static inline BlurGrid blur_grid(int r0, int r1, int nbx) {
   g.xcd = 0;
   g.r0 = r0;
   g.r1 = r1;
+  g.rows = nullptr;
+  g.part = kBlurWhole;
   if (const char* e = getenv("MW_BLUR_BH")) g.bh = atoi(e) >= 16 ? atoi(e) : kBlurMfmaBH;
   if (const char* e = getenv("MW_BLUR_XCD")) g.xcd = atoi(e);
   g.ntiles = nbx * ((r1 - r0 + g.bh - 1) / g.bh);
@@ -258,10 +268,42 @@ __global__ void __launch_bounds__(64 * BT * CT, 4) blur_mfma_kernel(const T* __r
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const int tx = wv % BT, ct = wv / BT;
   int bx, by;
-  bg.tile(blockIdx.x, gridDim.x, bx, by);
+  int blk = blockIdx.x;
+  bool below = false;  // kBlurRest: the second workgroup of a tile (the rows from b on)
+  if constexpr (EPI == kEpiStore) {
+    if (bg.part == kBlurRest && blk >= bg.ntiles) {
+      blk -= bg.ntiles;
+      below = true;
+    }
+  }
+  bg.tile(blk, EPI == kEpiStore ? bg.ntiles : (int)gridDim.x, bx, by);
   const int x0 = bx * BW;
-  const int y0 = bg.r0 + by * bg.bh;
-  const int y1 = min(bg.r1, y0 + bg.bh);
+  int y0 = bg.r0 + by * bg.bh;
+  int y1 = min(bg.r1, y0 + bg.bh);
+  if constexpr (EPI == kEpiStore) {
+    // Row range from the table: [a, b) (kBlurNeeded), or the band's rows above
+    // a / from b on (kBlurRest).  An output row has the same bits in whatever
+    // range it is computed: its horizontal rows depend on their input row
+    // alone (dma_row clamps to [0, H) of the slide, not to the range), and the
+    // vertical pass adds the 2r+1 taps in tap order wherever the row sits in
+    // the ring.  Only nrows depends on the range; a workgroup with no rows
+    // leaves here, before the first LDS write, DMA or barrier (the table entry
+    // comes by scalar loads: the test is uniform).
+    if (bg.rows != nullptr) {
+      const int ti = by * bg.nbx + bx;
+      const int a = max(y0, min(y1, bg.rows[2 * ti]));
+      const int b = max(a, min(y1, bg.rows[2 * ti + 1]));
+      if (bg.part == kBlurNeeded) {
+        y0 = a;
+        y1 = b;
+      } else if (below) {
+        y0 = b;
+      } else {
+        y1 = a;
+      }
+      if (y0 >= y1) return;
+    }
+  }
   const int nrows = (y1 - y0) + 2 * R;
   const int bw = min(BW, W - x0);
   // clamped input column range [xa, xb) and its position in the halo'd row
@@ -678,18 +720,24 @@ __global__ void __launch_bounds__(64 * BT * CT, 4) blur_mfma_kernel(const T* __r
 
 template <typename T, int R, int CT, int BT, int EPI, bool LOGN>
 static int launch_blur_mfma_one(const T* in, int H, int W, int C, const float* inv_mean, float p,
-                                const BlurTaps& taps, float* out, const BlurEpi& ep, hipStream_t st) {
+                                const BlurTaps& taps, float* out, const BlurEpi& ep, hipStream_t st,
+                                const int* rows = nullptr, int part = kBlurWhole) {
   using K = BlurMfmaCfg<T, R, CT, BT, EPI, LOGN && kBlurH16>;  // as the kernel instance
   const size_t lds = K::lds_bytes();
   if (lds > 160 * 1024 || K::D < 4) return MW_EUNSUPPORTED;
   const int nbx = (W + K::BW - 1) / K::BW;
   // the fused epilogues output the row window [ep.r0, ep.r1); img.blurring the whole array
-  const BlurGrid bg = EPI == kEpiStore ? blur_grid(0, H, nbx) : blur_grid(ep.r0, ep.r1, nbx);
+  BlurGrid bg = EPI == kEpiStore ? blur_grid(0, H, nbx) : blur_grid(ep.r0, ep.r1, nbx);
   if (bg.ntiles == 0) return MW_OK;
+  if (EPI == kEpiStore && rows != nullptr) {
+    bg.rows = rows;
+    bg.part = part;
+  }
+  const int nblocks = bg.part == kBlurRest ? 2 * bg.ntiles : bg.ntiles;
   BlurTaps tv = taps;  // H16: the vertical taps carry the 2^-24 descale (exact)
   if (LOGN && kBlurH16)
     for (int i = 0; i <= 2 * R; ++i) tv.w[i] = taps.w[i] * kH16VS;
-  hipLaunchKernelGGL((blur_mfma_kernel<T, R, CT, BT, LOGN, EPI>), dim3(bg.ntiles), dim3(K::NT), lds, st, in, H,
+  hipLaunchKernelGGL((blur_mfma_kernel<T, R, CT, BT, LOGN, EPI>), dim3(nblocks), dim3(K::NT), lds, st, in, H,
                      W, C, inv_mean, p, tv, out, ep, bg);
   MW_LAUNCH_CHECK();
   return MW_OK;
@@ -697,26 +745,28 @@ static int launch_blur_mfma_one(const T* in, int H, int W, int C, const float* i
 
 template <typename T, int R, int CT, int BT, int EPI>
 static int launch_blur_mfma_rc(const T* in, int H, int W, int C, const float* inv_mean, float p,
-                               const BlurTaps& taps, float* out, const BlurEpi& ep, hipStream_t st) {
-  if (inv_mean) return launch_blur_mfma_one<T, R, CT, BT, EPI, true>(in, H, W, C, inv_mean, p, taps, out, ep, st);
+                               const BlurTaps& taps, float* out, const BlurEpi& ep, hipStream_t st,
+                               const int* rows = nullptr, int part = kBlurWhole) {
+  if (inv_mean)
+    return launch_blur_mfma_one<T, R, CT, BT, EPI, true>(in, H, W, C, inv_mean, p, taps, out, ep, st, rows, part);
   if constexpr (EPI == kEpiStore)
-    return launch_blur_mfma_one<T, R, CT, BT, EPI, false>(in, H, W, C, inv_mean, p, taps, out, ep, st);
+    return launch_blur_mfma_one<T, R, CT, BT, EPI, false>(in, H, W, C, inv_mean, p, taps, out, ep, st, rows, part);
   return MW_EUNSUPPORTED;  // the fused epilogues follow a log-normalise
 }
 
 template <typename T, int R>
 static int launch_blur_mfma_r(const T* in, int H, int W, int C, const float* inv_mean, float p,
-                              const BlurTaps& taps, float* out, hipStream_t st) {
+                              const BlurTaps& taps, float* out, hipStream_t st, const int* rows, int part) {
   // column tiles per band: 4 (64-column bands, two 8-wave workgroups per CU
   // at C <= 32).  128-column bands (one 16-wave workgroup per CU, 12.5 % halo
   // instead of 25 %) are 3 % faster in a blur-only loop (3.91-3.93 vs
   // 4.04-4.06 ms) but 1.5-2.5 % slower inside the bench step (4.02-4.07 vs
   // 3.96-3.98 ms, same box, tools/dev/r3_bt_sweep.sh): not taken.
   const BlurEpi ep{};
-  if (C <= 16) return launch_blur_mfma_rc<T, R, 1, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st);
-  if (C <= 32) return launch_blur_mfma_rc<T, R, 2, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st);
-  if (C <= 48) return launch_blur_mfma_rc<T, R, 3, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st);
-  return launch_blur_mfma_rc<T, R, 4, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st);
+  if (C <= 16) return launch_blur_mfma_rc<T, R, 1, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st, rows, part);
+  if (C <= 32) return launch_blur_mfma_rc<T, R, 2, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st, rows, part);
+  if (C <= 48) return launch_blur_mfma_rc<T, R, 3, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st, rows, part);
+  return launch_blur_mfma_rc<T, R, 4, 4, kEpiStore>(in, H, W, C, inv_mean, p, taps, out, ep, st, rows, part);
 }
 
 // fused epilogue launch (BT = 4); the per-epilogue limits depend on CT
@@ -770,12 +820,13 @@ int launch_blur_epi(const T* in, int H, int W, int C, const float* inv_mean, flo
 // MW_EUNSUPPORTED otherwise (the caller tries the next path).
 template <typename T>
 int launch_blur_mfma(const T* in, int H, int W, int C, const float* inv_mean, float p,
-                     const BlurTaps& taps, int r, float* out, hipStream_t st) {
+                     const BlurTaps& taps, int r, float* out, hipStream_t st, const int* rows = nullptr,
+                     int part = kBlurWhole) {
   if (!blur_mfma_shape_ok(W, C, r, sizeof(T))) return MW_EUNSUPPORTED;
   if (const char* e = getenv("MW_BLUR_IMPL"))
     if (e[0] == 'v') return MW_EUNSUPPORTED;  // force the VALU kernel (A/B tests)
   switch (r) {
-#define MW_R(N) case N: return launch_blur_mfma_r<T, N>(in, H, W, C, inv_mean, p, taps, out, st);
+#define MW_R(N) case N: return launch_blur_mfma_r<T, N>(in, H, W, C, inv_mean, p, taps, out, st, rows, part);
     MW_R(1) MW_R(2) MW_R(3) MW_R(4) MW_R(5) MW_R(6) MW_R(7) MW_R(8)
 #undef MW_R
     default: return MW_EUNSUPPORTED;
@@ -790,6 +841,15 @@ int launch_blur_fast(const T* in, int H, int W, int C, const float* inv_mean, fl
   const int rc = launch_blur_mfma<T>(in, H, W, C, inv_mean, p, taps, r, out, st);
   if (rc != MW_EUNSUPPORTED) return rc;
   return launch_blur_valu<T>(in, H, W, C, inv_mean, p, taps, r, out, st);
+}
+
+// The matrix-core kernel over the row ranges of a table (mw_blur_rows_table):
+// part kBlurNeeded or kBlurRest.  MW_EUNSUPPORTED (nothing launched) for every
+// shape that kernel does not take: the other kernels blur whole slides only.
+template <typename T>
+int launch_blur_part(const T* in, int H, int W, int C, const float* inv_mean, float p,
+                     const BlurTaps& taps, int r, float* out, const int* rows, int part, hipStream_t st) {
+  return launch_blur_mfma<T>(in, H, W, C, inv_mean, p, taps, r, out, st, rows, part);
 }
 
 }  // namespace mw

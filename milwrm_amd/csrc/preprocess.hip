@@ -16,7 +16,7 @@
 #include <math.h>
 
 #include "common.h"
-#include "blur.h"
+#include "blur_mfma.h"
 
 namespace mw {
 
@@ -265,6 +265,12 @@ extern template int launch_blur_fast<uint16_t>(const uint16_t*, int, int, int, c
                                                const BlurTaps&, int, float*, hipStream_t);
 extern template int launch_blur_fast<float>(const float*, int, int, int, const float*, float,
                                             const BlurTaps&, int, float*, hipStream_t);
+extern template int launch_blur_part<uint8_t>(const uint8_t*, int, int, int, const float*, float, const BlurTaps&,
+                                              int, float*, const int*, int, hipStream_t);
+extern template int launch_blur_part<uint16_t>(const uint16_t*, int, int, int, const float*, float,
+                                               const BlurTaps&, int, float*, const int*, int, hipStream_t);
+extern template int launch_blur_part<float>(const float*, int, int, int, const float*, float, const BlurTaps&,
+                                            int, float*, const int*, int, hipStream_t);
 
 // Generic-radius fallback (r > kRingMax): two separable passes through an fp32
 // HWC temporary.  Pass 1 (axis 0): tmp[y,x,c] = sum_j w_j f(in[clamp(y+j-r),x,c]);
@@ -401,6 +407,65 @@ __global__ void __launch_bounds__(1024) mask_scan_kernel(uint32_t* __restrict__ 
     run += c;
   }
   if (t == 1023) *count = (int64_t)s[1023];
+}
+
+// ---------------------------------------------------------- blur row table
+// Which output rows of each blur tile (BlurGrid: BW columns x bh rows) the
+// labelling path can read.  A pixel is needed when its 64-aligned flat tile
+// (p >> 6, p = y W + x: it may wrap from one image row to the next) holds a
+// mask pixel: the tiles assign_kernel loads, which cover the gather's pixels.
+// One workgroup per blur tile; eight lanes share a row, 16 mask bytes each:
+// the row's pixels x0 .. x0 + bw - 1 (bw <= 64) lie in at most two flat
+// tiles, 128 bytes from the first tile's start, and the row is needed when
+// any of their bytes is set.  tab[2 t], tab[2 t + 1] = the hull [a, b) of the
+// needed rows of tile t (a = b = the band's first row: none).
+constexpr int kBlurTableBW = 64;  // column band of the store kernel (BT = 4)
+
+__global__ void __launch_bounds__(256) blur_rows_table_kernel(const uint8_t* __restrict__ m, int H, int W,
+                                                              int bh, int nbx, int* __restrict__ tab) {
+  __shared__ int s_lo, s_hi;
+  const int by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
+  const int y0 = by * bh, y1 = min(H, y0 + bh);
+  const int x0 = bx * kBlurTableBW, bw = min(kBlurTableBW, W - x0);
+  const int64_t n = (int64_t)H * W;
+  const bool al16 = (reinterpret_cast<uintptr_t>(m) & 15) == 0;
+  const int g = threadIdx.x >> 3, sub = threadIdx.x & 7;
+  if (threadIdx.x == 0) {
+    s_lo = y1;
+    s_hi = y0;
+  }
+  __syncthreads();
+  int lo = y1, hi = y0;
+  for (int yb = y0; yb < y1; yb += 32) {
+    const int y = yb + g;
+    bool any = false;
+    if (y < y1) {
+      const int64_t p0 = (int64_t)y * W + x0;
+      const int64_t e = min(n, (((p0 + bw - 1) >> 6) + 1) << 6);  // end of the row's last flat tile
+      const int64_t q0 = ((p0 >> 6) << 6) + 16 * sub;
+      if (q0 + 16 <= e && al16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(m + q0);
+        any = (v.x | v.y | v.z | v.w) != 0;
+      } else {
+        for (int64_t q = q0; q < min(e, q0 + 16); ++q) any |= m[q] != 0;
+      }
+    }
+    const unsigned long long bal = __ballot(any);
+    if (y < y1 && ((bal >> (threadIdx.x & 56)) & 0xffull) != 0) {
+      lo = min(lo, y);
+      hi = max(hi, y + 1);
+    }
+  }
+  if (sub == 0 && lo < hi) {
+    atomicMin(&s_lo, lo);
+    atomicMax(&s_hi, hi);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const bool none = s_lo >= s_hi;
+    tab[2 * blockIdx.x] = none ? y0 : s_lo;
+    tab[2 * blockIdx.x + 1] = none ? y0 : s_hi;
+  }
 }
 
 // ------------------------------------------------------------ rank index
@@ -1013,6 +1078,40 @@ int mw_blur(const void* d_img, int dtype, int H, int W, int C, const float* d_in
     case MW_U16: return launch_blur<uint16_t>((const uint16_t*)d_img, H, W, C, d_inv_mean, pseudoval, taps, radius, d_out, tmp, st);
     case MW_F32: return launch_blur<float>((const float*)d_img, H, W, C, d_inv_mean, pseudoval, taps, radius, d_out, tmp, st);
     default: set_error("mw_blur: bad dtype %d", dtype); return MW_EINVAL;
+  }
+}
+
+int mw_blur_rows_tiles(int H, int W) {
+  if (H <= 0 || W <= 0) return 0;
+  return blur_grid(0, H, (W + kBlurTableBW - 1) / kBlurTableBW).ntiles;
+}
+
+int mw_blur_rows_table(const uint8_t* d_mask, int H, int W, int32_t* d_table, void* stream) {
+  MW_CHECK_ARG(d_mask && d_table, "mw_blur_rows_table: null pointer");
+  MW_CHECK_ARG(H > 0 && W > 0, "mw_blur_rows_table: bad shape %dx%d", H, W);
+  const BlurGrid bg = blur_grid(0, H, (W + kBlurTableBW - 1) / kBlurTableBW);
+  hipLaunchKernelGGL(blur_rows_table_kernel, dim3(bg.ntiles), dim3(256), 0, as_stream(stream), d_mask, H, W,
+                     bg.bh, bg.nbx, d_table);
+  MW_LAUNCH_CHECK();
+  return MW_OK;
+}
+
+int mw_blur_part(const void* d_img, int dtype, int H, int W, int C, const float* d_inv_mean, float pseudoval,
+                 const float* h_w, int radius, float* d_out, const int32_t* d_table, int part, void* stream) {
+  MW_CHECK_ARG(d_img && d_out && h_w && d_table, "mw_blur_part: null pointer");
+  MW_CHECK_ARG(H > 0 && W > 0 && C > 0, "mw_blur_part: bad shape %dx%dx%d", H, W, C);
+  MW_CHECK_ARG(d_img != (const void*)d_out, "mw_blur_part: out must not alias in");
+  MW_CHECK_ARG(part == kBlurNeeded || part == kBlurRest, "mw_blur_part: bad part %d", part);
+  if (radius < 1 || radius > kBlurMfmaMaxR) return MW_EUNSUPPORTED;
+  BlurTaps taps;
+  memset(&taps, 0, sizeof(taps));
+  for (int j = 0; j <= 2 * radius; ++j) taps.w[j] = h_w[j];
+  hipStream_t st = as_stream(stream);
+  switch (dtype) {
+    case MW_U8: return launch_blur_part<uint8_t>((const uint8_t*)d_img, H, W, C, d_inv_mean, pseudoval, taps, radius, d_out, d_table, part, st);
+    case MW_U16: return launch_blur_part<uint16_t>((const uint16_t*)d_img, H, W, C, d_inv_mean, pseudoval, taps, radius, d_out, d_table, part, st);
+    case MW_F32: return launch_blur_part<float>((const float*)d_img, H, W, C, d_inv_mean, pseudoval, taps, radius, d_out, d_table, part, st);
+    default: set_error("mw_blur_part: bad dtype %d", dtype); return MW_EINVAL;
   }
 }
 

@@ -471,6 +471,58 @@ def blur(img: torch.Tensor, sigma: float, inv_mean=None, pseudoval: float = 1.0,
     return out
 
 
+BLUR_REST_USED = {"rest": 0}  # completions of a partly blurred image (blur_rest), for tests
+
+
+def blur_rows_table(mask_u8: torch.Tensor) -> torch.Tensor:
+    """Per workgroup tile of the matrix-core blur the hull [a, b) of its output
+    rows that hold a needed pixel -- one whose 64-aligned flat tile holds a
+    pixel of the H x W uint8 ``mask_u8`` (mw_blur_rows_table):
+    int32 [tiles, 2] on the device, never read by the host."""
+    H, W = mask_u8.shape
+    tab = torch.empty((N.query("mw_blur_rows_tiles", H, W), 2), dtype=torch.int32, device=mask_u8.device)
+    N.call("mw_blur_rows_table", P(mask_u8), H, W, P(tab), stream())
+    return tab
+
+
+def blur_needed(img: torch.Tensor, sigma: float, mask_u8: torch.Tensor, inv_mean=None, pseudoval: float = 1.0,
+                truncate: float = 4.0, out=None):
+    """``blur`` of the rows the labelling path can read (the hulls of
+    ``blur_rows_table(mask_u8)``); the other rows of the output stay unwritten
+    until ``blur_rest``.  Returns (out, rest), ``rest`` the arguments of the
+    completion -- or (the whole blur, None) for shapes the matrix-core kernel
+    does not take.  The ``blur`` region is credited the whole slide's bytes."""
+    H, W, C = img.shape
+    w = gaussian_taps(sigma, truncate)
+    r = (len(w) - 1) // 2
+    # the matrix-core kernel's shape limits (mw_blur_part), checked before the table is built
+    takes = (C % 2 == 0 and C <= 64 and 1 <= r <= 8 and (W * C) % 4 == 0
+             and os.environ.get("MW_BLUR_IMPL", "")[:1] != "v")
+    if not takes or not img.is_contiguous() or not mask_u8.is_contiguous() or tuple(mask_u8.shape) != (H, W):
+        return blur(img, sigma, inv_mean=inv_mean, pseudoval=pseudoval, out=out, truncate=truncate), None
+    tab = blur_rows_table(mask_u8)
+    if out is None:
+        out = torch.empty((H, W, C), dtype=torch.float32, device=img.device)
+    with profiling.timed("blur", H * W * C * (img.element_size() + 4)):
+        ok = N.try_call("mw_blur_part", P(img), dtype_code(img), H, W, C, P(inv_mean), float(pseudoval),
+                        w.ctypes.data, r, P(out), P(tab), 1, stream())
+    if not ok:
+        return blur(img, sigma, inv_mean=inv_mean, pseudoval=pseudoval, out=out, truncate=truncate), None
+    return out, (img, w, r, inv_mean, float(pseudoval), tab)
+
+
+def blur_rest(out: torch.Tensor, rest) -> torch.Tensor:
+    """Blur the rows ``blur_needed`` left out into ``out``: the whole blur,
+    bit for bit."""
+    img, w, r, inv_mean, pseudoval, tab = rest
+    H, W, C = img.shape
+    BLUR_REST_USED["rest"] += 1
+    with profiling.timed("blur_rest", 0):
+        N.call("mw_blur_part", P(img), dtype_code(img), H, W, C, P(inv_mean), pseudoval, w.ctypes.data, r,
+               P(out), P(tab), 2, stream())
+    return out
+
+
 def median_size(size):
     """``size`` of a median window as (rows, cols): an int or a pair of ints,
     each at least 1 (ValueError otherwise; no device call)."""
