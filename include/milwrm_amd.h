@@ -15,7 +15,8 @@
  *   mw_lognorm         img.log_normalize                  MxIF.py:416-455
  *   mw_blur            img.blurring('gaussian') → skimage.filters.gaussian →
  *                      scipy.ndimage.gaussian_filter       MxIF.py:375-394
- *   mw_clahe           img.equalize_hist → skimage equalize_adapthist
+ *   mw_clahe,
+ *   mw_clahe_rows_*    img.equalize_hist → skimage equalize_adapthist
  *                                                          MxIF.py:95-122, 360-373
  *   mw_block_mean,
  *   mw_block_reduce_rows img.downsample → skimage block_reduce MxIF.py:494-517
@@ -157,6 +158,56 @@ size_t mw_clahe_ws_bytes(int H, int W, int C, int kh, int kw, int nbins);
 int mw_clahe(const void* d_img, int dtype, int H, int W, int C, const int* h_enable,
              int kh, int kw, double clip_limit, int nbins, float* d_out,
              void* d_ws, int* d_luts_out, void* stream);
+/* The same equalisation of a slide that is handed over in bands of rows (a
+ * slide streamed from the host, stream.clahe / stream.ClaheSource; DESIGN.md
+ * §26).  d_state: mw_clahe_ws_bytes(H, W, C, kh, kw, nbins) bytes, 16-byte
+ * aligned, kept from begin until the last map (the key minima and maxima, the
+ * [C][nby][nbx][nbins] counts that become the tables in place, the blend's
+ * extremes, the rescale rows).  In this order, every band once per loop:
+ *   mw_clahe_rows_begin     checks the arguments as mw_clahe, clears the state
+ *   mw_clahe_rows_range     adds a band to the planes' minima and maxima
+ *   mw_clahe_rows_hist      counts a band into the tiles' histograms: slide row
+ *                           y into tile row y / kh and, when r = 2 H - 2 - y
+ *                           lies in [H, nby kh), once more into tile row
+ *                           nby - 1 (the rows past the image reflect; as
+ *                           nby kh - H < kh <= H a row reflects at most once)
+ *   mw_clahe_rows_luts      after the last band: the counts become the tables
+ *                           (d_luts_out as mw_clahe's, may be NULL)
+ *   mw_clahe_rows_extremes  the map pass of a band without a store: only the
+ *                           minimum and maximum of every plane's blend are kept
+ *   mw_clahe_rows_finish    after the last band: the rescale rows
+ *   mw_clahe_rows_map       writes a band's final fp32 pixels to d_out (rows x
+ *                           W x C): the blend and the rescale in one kernel,
+ *                           the rescale evaluated as mw_rescale's mode 3
+ * The minima, maxima and counts are integer atomics (the blend's extremes
+ * integer atomics on fp32 bits), the tables and the map are mw_clahe's code, so
+ * tables and pixels are bit for bit mw_clahe's of the whole slide whatever the
+ * bands and their order.  d_rows: the slide's rows [y0, y0 + rows), contiguous,
+ * aligned to its element type only (a band that is a view into a resident
+ * slide starts anywhere; the kernels take their vector phase from the
+ * address); d_out: aligned to 4 bytes, and it may be d_rows itself for an fp32
+ * band (no other overlap).  dtype, H, W, C, h_enable, kh, kw, clip_limit and
+ * nbins as mw_clahe, the same values in every call of one equalisation.
+ * MW_EINVAL also for rows < 1, y0 < 0, y0 + rows > H and a null state;
+ * MW_EUNSUPPORTED as mw_clahe; all found before any device call.  Nothing
+ * returns to the host between the calls; all of them on one stream (or
+ * ordered by the caller). */
+int mw_clahe_rows_begin(int dtype, int H, int W, int C, int kh, int kw, double clip_limit,
+                        int nbins, void* d_state, void* stream);
+int mw_clahe_rows_range(const void* d_rows, int dtype, int rows, int W, int C,
+                        void* d_state, void* stream);
+int mw_clahe_rows_hist(const void* d_rows, int dtype, int y0, int rows, int H, int W, int C,
+                       const int* h_enable, int kh, int kw, int nbins, void* d_state,
+                       void* stream);
+int mw_clahe_rows_luts(int H, int W, int C, int kh, int kw, double clip_limit, int nbins,
+                       void* d_state, int* d_luts_out, void* stream);
+int mw_clahe_rows_extremes(const void* d_rows, int dtype, int y0, int rows, int H, int W,
+                           int C, const int* h_enable, int kh, int kw, int nbins,
+                           void* d_state, void* stream);
+int mw_clahe_rows_finish(int C, const int* h_enable, void* d_state, void* stream);
+int mw_clahe_rows_map(const void* d_rows, int dtype, int y0, int rows, int H, int W, int C,
+                      const int* h_enable, int kh, int kw, int nbins, void* d_state,
+                      float* d_out, void* stream);
 
 /* ---- img.blurring('median', size=k) (MxIF.py:395-405 as intended) -----------
  * Median filter per channel over a size_y x size_x window (rows y - size_y/2

@@ -121,6 +121,7 @@ class img:
     # (``_finish_blur()``, or read ``img``) before editing a mask in place.
     _dev_t = None
     _blur_rest = None
+    _pending_clahe = None
 
     @property
     def _dev(self):
@@ -161,7 +162,7 @@ class img:
         from .stream import RESIDENCY
 
         if (self._blur_rest is not None and self._pending is None and self._pending_rescale is None
-                and not self._filter_deferred()):
+                and self._pending_clahe is None and not self._filter_deferred()):
             RESIDENCY.touch(self)
             return self._dev_t
         return D.as_float32(self._materialize())
@@ -177,6 +178,10 @@ class img:
         # deferred clip / scale rounds, applied before anything else pending (stream.RescaleSource):
         # (host [C, 5] D.rescale tables, the same on the device)
         self._pending_rescale = None
+        # deferred equalize_hist(banded=True) rounds, applied after the clip / scale rounds and before anything
+        # else pending (stream.ClaheSource): a list of (finished D.ClaheRows, kernel_size, clip_limit, nbins,
+        # the round's channels), never changed in place
+        self._pending_clahe = None
         self._range = None          # per-channel (lo, hi) of clipped / scaled pixels (NaN: not known), see _blur_bound
         self._pending = None        # (inv_mean fp32 device tensor, pseudoval) deferred log_normalize
         self._pending_blur = None   # (sigma, truncate) deferred gaussian (fused-epilogue mode)
@@ -229,7 +234,7 @@ class img:
         """Bytes per element of the pixels as the device holds (or would hold) them."""
         from .stream import device_dtype_of
 
-        if self._pending_rescale is not None:
+        if self._pending_rescale is not None or self._pending_clahe is not None:
             return 4
         if self._dev_t is not None:
             return self._dev_t.element_size()
@@ -270,24 +275,31 @@ class img:
                 f"this operation needs the whole raw slide in HBM ({nbytes / 2**30:.1f} GiB) and "
                 f"{have / 2**30:.1f} GiB can be allocated: the slide is streamed in row bands instead by "
                 f"the passes that take bands (clip and scale of raw or clipped / scaled pixels, "
-                f"calculate_non_zero_mean, log_normalize + blurring with the "
+                f"equalize_hist(banded=True) of those, calculate_non_zero_mean, log_normalize + blurring with the "
                 f"default batch mean, subsample_pixels, create_tissue_mask, downsample, label_tissue_regions, "
-                f"confidence_score_images; not clip or scale after a log_normalize or a filter, nor "
-                f"equalize_hist)")
+                f"confidence_score_images; not clip, scale or equalize_hist after a log_normalize or a filter, "
+                f"nor clip or scale after a deferred equalize_hist)")
 
     def _source(self):
         """None when the pixels are resident (or the raw ones are admitted now:
         the caller then takes ``_device()``); else the ``stream.RowSource`` to
-        read them from band by band.  With clip / scale rounds deferred that is
-        always a source: the raw one -- the resident raw slide, if it is --
-        seen through the rounds (``stream.RescaleSource``)."""
-        from .stream import DeviceSource, RescaleSource
+        read them from band by band.  With clip / scale or equalize_hist rounds
+        deferred that is always a source: the raw one -- the resident raw
+        slide, if it is -- seen through the clip / scale rounds
+        (``stream.RescaleSource``), then through one ``stream.ClaheSource``
+        per equalize_hist round."""
+        from .stream import ClaheSource, DeviceSource, RescaleSource
 
-        base = self._raw_source()
-        if self._pending_rescale is None:
-            return base
-        return RescaleSource(base if base is not None else DeviceSource(self._device()),
-                             self._pending_rescale[1])
+        src = self._raw_source()
+        if self._pending_rescale is None and self._pending_clahe is None:
+            return src
+        if src is None:
+            src = DeviceSource(self._device())
+        if self._pending_rescale is not None:
+            src = RescaleSource(src, self._pending_rescale[1])
+        for rnd in self._pending_clahe or ():
+            src = ClaheSource(src, rnd[0])
+        return src
 
     def _raw_source(self):
         """``_source`` of the raw pixels (before any deferred clip / scale)."""
@@ -328,6 +340,7 @@ class img:
         obj._host64 = None
         obj._dev = None
         obj._pending_rescale = None
+        obj._pending_clahe = None
         obj._range = None
         obj._pending = None
         obj._pending_blur = None
@@ -359,9 +372,10 @@ class img:
         """Apply a deferred blur (with its log_normalize fused), a deferred
         median (the log_normalize as its epilogue), a deferred bilateral (the
         log_normalize as its load) or a deferred log_normalize (standalone
-        kernel).  Deferred clip / scale rounds apply first, then what else
-        is pending on their fp32 result, as one evictable transform."""
-        if self._pending_rescale is not None:
+        kernel).  Deferred clip / scale rounds apply first, then deferred
+        equalize_hist rounds, then what else is pending on their fp32 result,
+        as one evictable transform."""
+        if self._pending_rescale is not None or self._pending_clahe is not None:
             rng = self._range if self._pending is None and not self._filter_deferred() else None
             self._transformed(self._apply_rescaled)
             self._range = rng
@@ -398,10 +412,14 @@ class img:
 
     def _apply_rescaled(self) -> torch.Tensor:
         """The pixels with everything pending applied, the deferred clip /
-        scale rounds first: the calls of the resident path, in its order."""
+        scale rounds first, then the deferred equalize_hist rounds (each whole,
+        D.clahe: the banded form's bits): the calls of the resident path, in
+        its order."""
         t = self._device()  # (a slide that is not resident and does not fit: _device()'s MemoryError)
-        for i, tab in enumerate(self._pending_rescale[1]):
+        for i, tab in enumerate(self._pending_rescale[1] if self._pending_rescale is not None else ()):
             t = D.rescale(t, tab, out=t if i else None)
+        for _, kernel_size, clip_limit, nbins, chs in self._pending_clahe or ():
+            t = D.clahe(t, kernel_size, clip_limit, nbins, enable=chs)
         inv, p = self._pending if self._pending is not None else (None, 1.0)
         if self._pending_bilateral is not None:
             sigma, sigma_color, win_size, mode, cval = self._pending_bilateral
@@ -423,9 +441,11 @@ class img:
 
         backed = self._host is not None or self._src is not None
         state = (self._host, self._src, self._pending, self._pending_blur,
-                 self._pending_median, self._pending_bilateral, self._pending_rescale, self._range) if backed else None
+                 self._pending_median, self._pending_bilateral, self._pending_rescale, self._pending_clahe,
+                 self._range) if backed else None
         out = make()
         self._pending_rescale = None
+        self._pending_clahe = None
         self._pending = None
         self._pending_blur = None
         self._pending_median = None
@@ -455,7 +475,7 @@ class img:
         rv = getattr(self, "_revert", None)
         if rv is not None:
             (self._host, self._src, self._pending, self._pending_blur, self._pending_median,
-             self._pending_bilateral, self._pending_rescale, self._range) = rv
+             self._pending_bilateral, self._pending_rescale, self._pending_clahe, self._range) = rv
             self._revert = None
             self._host64 = None
         self._dev = None
@@ -466,7 +486,8 @@ class img:
         if self._host64 is None:
             if (self._dev is None and self._host is not None and self._pending is None
                     and self._pending_blur is None and self._pending_median is None
-                    and self._pending_bilateral is None and self._pending_rescale is None):
+                    and self._pending_bilateral is None and self._pending_rescale is None
+                    and self._pending_clahe is None):
                 self._host64 = self._host.astype("float64")
             else:
                 t = self._materialize()
@@ -487,6 +508,7 @@ class img:
         self._src = None
         self._hsrc = None
         self._pending_rescale = None
+        self._pending_clahe = None
         self._range = None
         self._pending = None
         self._pending_blur = None
@@ -588,6 +610,7 @@ class img:
         obj._host64 = None
         obj._dev = tensor
         obj._pending_rescale = None
+        obj._pending_clahe = None
         obj._range = None
         obj._pending = None
         obj._pending_blur = None
@@ -692,8 +715,9 @@ class img:
         pass that needs pixels rescales each band as it reads it
         (stream.RescaleSource), before a later log_normalize or filter: the
         resident bits.  With a log_normalize or a filter already pending the
-        pixels are materialised first (MemoryError when they do not fit); a
-        row band of a slide split over ranks is refused."""
+        pixels are materialised first (MemoryError when they do not fit), and
+        so are deferred equalize_hist rounds; a row band of a slide split over
+        ranks is refused."""
         from . import stream
 
         if getattr(self, "_band", None) is not None:
@@ -702,7 +726,7 @@ class img:
         rounds = self._channel_rounds(channels)
         deferred = False
         rng = np.full((2, self.n_ch), np.nan)  # after a log_normalize or a filter: not known
-        if self._pending is None and not self._filter_deferred():
+        if self._pending is None and not self._filter_deferred() and self._pending_clahe is None:
             rng = self._range_now()
             H, W = self.shape[0], self.shape[1]
             deferred = self._source() is not None or not self._may_hold(H * W * self.n_ch * 4)
@@ -793,25 +817,66 @@ class img:
         ``nbins`` (256, at most 256) as skimage's.  ``channels`` as ``clip``:
         None (or a 2-D image) means every plane, else indices or names, the
         other planes unchanged; a plane listed twice is equalised twice.  The
-        pixels become fp32.  The slide must be resident: deferred clip /
-        scale rounds are materialised first (MemoryError when that does not
-        fit); there is no banded form."""
+        pixels become fp32.
+
+        ``banded=False``: the slide must be resident: deferred clip / scale
+        rounds are materialised first (MemoryError when that does not fit).
+        ``banded=True`` permits the banded form: raw pixels (or
+        ones whose only pending state is earlier clip / scale / equalize_hist
+        rounds) that are not resident, or whose fp32 result may not be held
+        (the HBM budget), keep the rounds deferred (``_pending_clahe``).  The
+        call reads the slide three times per round (the planes' ranges, the
+        tiles' histograms, the extremes of the blend: stream.clahe) and keeps
+        the tables in HBM (MemoryError when they do not fit: a larger
+        ``kernel_size`` makes them smaller); every pass that needs pixels then
+        equalises each band as it reads it (stream.ClaheSource), before a
+        later log_normalize or filter, with the resident bits.  A resident
+        slide whose result may be held is equalised at once, exactly as with
+        ``banded=False``; so is one with a log_normalize or a filter already
+        pending (materialised first, MemoryError when it does not fit)."""
         if "kernel_size" not in kwargs:  # also for the unbound call with no arguments at all
             raise _need_kernel_size("img.equalize_hist")
         kernel_size = kwargs.pop("kernel_size")
         clip_limit = kwargs.pop("clip_limit", 0.01)
         nbins = kwargs.pop("nbins", 256)
+        banded = bool(kwargs.pop("banded", False))
         if kwargs:
-            raise NotImplementedError(f"equalize_hist options {kwargs} (kernel_size, clip_limit and nbins are "
-                                      "implemented)")
+            raise NotImplementedError(f"equalize_hist options {kwargs} (kernel_size, clip_limit, nbins and banded "
+                                      "are implemented)")
         if getattr(self, "_band", None) is not None:
             raise NotImplementedError("equalize_hist of a row band of a slide: the tiles and the extremes are the "
                                       "whole slide's")
-        D.clahe_args(self.shape[0], self.shape[1], kernel_size, clip_limit, nbins)  # before any device call
+        H, W = self.shape[0], self.shape[1]
+        kh, kw, clip_limit, nbins = D.clahe_args(H, W, kernel_size, clip_limit, nbins)  # before any device call
+        if banded and self._pending is None and not self._filter_deferred():
+            src = self._source()
+            if src is not None or not self._may_hold(H * W * self.n_ch * 4):
+                self._equalize_deferred(src, channels, (kh, kw), clip_limit, nbins)
+                return
         t = self._materialize()  # a slide that is not resident: _device()'s MemoryError
         for chs in self._channel_rounds(channels):
             t = D.clahe(t, kernel_size, clip_limit, nbins, enable=chs)
         self._set_device(t)
+        self._xbound = None
+        self._lognorm_host = None
+
+    def _equalize_deferred(self, src, channels, kernel, clip_limit, nbins):
+        """The banded form of ``equalize_hist``: per round the statistics now,
+        band by band over ``src`` (None: the resident raw slide as a source)
+        seen through the rounds before it, then the round stays deferred.
+        ``_range`` is left as the resident call leaves it: not known."""
+        from . import stream
+
+        if src is None:
+            src = stream.DeviceSource(self._device())
+        rounds = list(self._pending_clahe or ())
+        for chs in self._channel_rounds(channels):
+            state = stream.clahe(src, kernel, clip_limit, nbins, enable=chs)
+            rounds.append((state, kernel, clip_limit, nbins, chs))
+            src = stream.ClaheSource(src, state)
+        self._pending_clahe = rounds
+        self._host64 = None
+        self._range = None
         self._xbound = None
         self._lognorm_host = None
 
@@ -995,7 +1060,7 @@ class img:
         are a raw uint8 / uint16 slide (device, host or streamed), else None."""
         if self._pending_blur is not None or self._pending_bilateral is not None:
             return None
-        if self._pending_rescale is not None:
+        if self._pending_rescale is not None or self._pending_clahe is not None:
             return None
         if self._dev_t is not None:
             t = self._dev_t.dtype
@@ -1197,6 +1262,7 @@ class img:
             out = stream.downsample(src, fact, func, filt)
             self._pending = self._pending_blur = self._pending_median = self._pending_bilateral = None
             self._pending_rescale = None
+            self._pending_clahe = None
             self._lognorm_host = None
         else:
             out = D.block_reduce(self._materialize(), fact, func)

@@ -47,6 +47,16 @@ _PROTOS = {
     "mw_clahe_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "mw_clahe": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, C.c_double, c_i32, c_vp, c_vp, c_vp,
                          c_vp]),
+    "mw_clahe_rows_begin": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, c_vp, c_vp]),
+    "mw_clahe_rows_range": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mw_clahe_rows_hist": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp,
+                                   c_vp]),
+    "mw_clahe_rows_luts": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, c_vp, c_vp, c_vp]),
+    "mw_clahe_rows_extremes": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32,
+                                       c_vp, c_vp]),
+    "mw_clahe_rows_finish": (c_i32, [c_i32, c_vp, c_vp, c_vp]),
+    "mw_clahe_rows_map": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp,
+                                  c_vp, c_vp]),
     "mw_median_is_network": (c_i32, [c_i32, c_i32]),
     "mw_median": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),
     "mw_median_generic": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp]),

@@ -447,6 +447,101 @@ def clahe(img: torch.Tensor, kernel_size, clip_limit=0.01, nbins=256, enable=Non
     return (out, lut) if luts else out
 
 
+class ClaheRows:
+    """``clahe`` of a slide that is handed over in bands of rows
+    (mw_clahe_rows_*; stream.clahe, stream.ClaheSource).  Three
+    loops over the bands, every band once in each: ``range``; ``hist``, then
+    ``luts``; ``extremes``, then ``finish``.  After that ``map`` writes any
+    band's final fp32 pixels, bit for bit the rows ``clahe`` gives for the
+    whole slide, whatever the bands.  The object owns the state (the tables
+    among them) for as long as bands are mapped.  A band is a contiguous
+    [rows, W, C] tensor of the slide's element type that may start anywhere (a
+    view into a resident slide: no 16-byte alignment is asked).  Arguments are
+    checked on the host first (``clahe_args``); nothing is synchronised."""
+
+    def __init__(self, dtype, H: int, W: int, C: int, kernel_size, clip_limit=0.01, nbins=256, enable=None,
+                 dev=None):
+        try:
+            self.code = _DTYPE_CODE[dtype]
+        except KeyError:
+            raise TypeError(f"unsupported device image dtype {dtype}") from None
+        self.dtype, self.H, self.W, self.C = dtype, int(H), int(W), int(C)
+        self.kh, self.kw, self.clip_limit, self.nbins = clahe_args(H, W, kernel_size, clip_limit, nbins)
+        self.en = None
+        if enable is not None:
+            self.en = np.zeros(self.C, dtype=np.int32)
+            self.en[np.asarray(list(enable), dtype=np.int64)] = 1
+        self.elem = torch.empty(0, dtype=dtype).element_size()
+        self.finished = False
+        dev = device() if dev is None else dev
+        self.state = torch.empty(self.state_bytes(H, W, C, self.kh, self.kw, self.nbins), dtype=torch.uint8,
+                                 device=dev)
+        N.call("mw_clahe_rows_begin", self.code, self.H, self.W, self.C, self.kh, self.kw, self.clip_limit,
+               self.nbins, P(self.state), stream())
+
+    @staticmethod
+    def state_bytes(H, W, C, kh, kw, nbins) -> int:
+        return N.query("mw_clahe_ws_bytes", int(H), int(W), int(C), int(kh), int(kw), int(nbins))
+
+    def _en(self):
+        return None if self.en is None else self.en.ctypes.data
+
+    def _band(self, rows: torch.Tensor, y0: int) -> int:
+        if rows.dtype != self.dtype or tuple(rows.shape[1:]) != (self.W, self.C):
+            raise ValueError(f"clahe: a band must be [rows, {self.W}, {self.C}] of {self.dtype}, got "
+                             f"{tuple(rows.shape)} of {rows.dtype}")
+        if not rows.is_contiguous():
+            raise ValueError("clahe: the band must be contiguous")
+        n = int(rows.shape[0])
+        if n < 1 or y0 < 0 or y0 + n > self.H:
+            raise ValueError(f"clahe: the band's rows [{y0}, {y0 + n}) are not rows of the {self.H}-row slide")
+        return n
+
+    def range(self, rows: torch.Tensor):
+        n = self._band(rows, 0)
+        with profiling.timed("clahe_range", n * self.W * self.C * self.elem):
+            N.call("mw_clahe_rows_range", P(rows), self.code, n, self.W, self.C, P(self.state), stream())
+
+    def hist(self, rows: torch.Tensor, y0: int):
+        n = self._band(rows, y0)
+        with profiling.timed("clahe_hist", n * self.W * self.C * self.elem):
+            N.call("mw_clahe_rows_hist", P(rows), self.code, int(y0), n, self.H, self.W, self.C, self._en(), self.kh,
+                   self.kw, self.nbins, P(self.state), stream())
+
+    def luts(self, out: bool = False):
+        """The counts become the tables; ``out``: return them, int32 [C, nby, nbx, nbins]."""
+        lut = None
+        if out:
+            lut = torch.empty((self.C, -(-self.H // self.kh), -(-self.W // self.kw), self.nbins), dtype=torch.int32,
+                              device=self.state.device)
+        N.call("mw_clahe_rows_luts", self.H, self.W, self.C, self.kh, self.kw, self.clip_limit, self.nbins,
+               P(self.state), P(lut), stream())
+        return lut
+
+    def extremes(self, rows: torch.Tensor, y0: int):
+        n = self._band(rows, y0)
+        with profiling.timed("clahe_extremes", n * self.W * self.C * self.elem):
+            N.call("mw_clahe_rows_extremes", P(rows), self.code, int(y0), n, self.H, self.W, self.C, self._en(),
+                   self.kh, self.kw, self.nbins, P(self.state), stream())
+
+    def finish(self):
+        N.call("mw_clahe_rows_finish", self.C, self._en(), P(self.state), stream())
+        self.finished = True
+
+    def map(self, rows: torch.Tensor, y0: int, out: torch.Tensor) -> torch.Tensor:
+        """The final pixels of the band into ``out`` (fp32, the band's shape;
+        it may be the band itself when that is fp32)."""
+        n = self._band(rows, y0)
+        if not self.finished:
+            raise ValueError("clahe: map before finish")
+        if out.dtype != torch.float32 or out.shape != rows.shape or not out.is_contiguous():
+            raise ValueError(f"clahe: out must be a contiguous float32 tensor of shape {tuple(rows.shape)}")
+        with profiling.timed("clahe_map", n * self.W * self.C * (self.elem + 4)):
+            N.call("mw_clahe_rows_map", P(rows), self.code, int(y0), n, self.H, self.W, self.C, self._en(), self.kh,
+                   self.kw, self.nbins, P(self.state), P(out), stream())
+        return out
+
+
 def gaussian_taps(sigma: float, truncate: float = 4.0) -> np.ndarray:
     """scipy ``_gaussian_kernel1d`` order 0 (radius int(truncate*sigma+0.5)),
     computed in fp64 then rounded to fp32 for the kernel."""
@@ -932,6 +1027,9 @@ MEDIAN_USED = {"network": 0, "generic": 0, "rows_streamed": 0}
 INTENSITY_USED = {"select_streamed": 0, "rescale_streamed": 0}
 # bands of a slide that is not resident filtered by the deferred bilateral (stream.BilateralBand)
 BILATERAL_USED = {"rows_streamed": 0}
+# equalisations whose statistics were gathered band by band from a slide that is not resident
+# (stream.clahe); bands equalised on their way in (stream.ClaheSource)
+CLAHE_USED = {"stats_streamed": 0, "map_streamed": 0}
 
 
 def defer_blur(H: int, W: int, C: int) -> bool:

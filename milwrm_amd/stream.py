@@ -37,7 +37,12 @@ Here:
   percentiles band by band (``quantiles``: integer histograms, the whole
   slide's bits) and stay deferred as a ``RescaleSource``: a source that wraps
   the raw one and hands every band on rescaled, so every pass above takes it
-  unchanged (tests/test_gpu_intensity_stream.py).
+  unchanged (tests/test_gpu_intensity_stream.py);
+* ``img.equalize_hist(kernel_size=k, banded=True)`` of such a slide gathers
+  its statistics band by band (``clahe``: the planes' ranges, the tiles'
+  histograms, the extremes of the blend, all integer reductions) and stays
+  deferred as one ``ClaheSource`` per round on top of the ``RescaleSource``
+  (tests/test_gpu_clahe_stream.py).
 
 Sources (``RowSource``): ``DeviceSource`` (a resident tensor; its bands are
 views, no copy), ``HostSource`` (a host array: pinned memory -- e.g.
@@ -351,6 +356,48 @@ class RescaleSource(RowSource):
         return self.inner.mask_device()
 
 
+class ClaheSource(RowSource):
+    """A slide seen through one deferred ``img.equalize_hist(banded=True)``
+    round: ``inner``'s rows mapped by the finished ``state`` (device.ClaheRows
+    after ``stream.clahe``; mw_clahe_rows_map: the blend and its rescale in
+    one kernel) as fp32, the resident equalisation's bits.  As
+    ``RescaleSource``: the band is read into a staging buffer of the inner
+    element type (an fp32 band straight into ``out`` and mapped in place, a
+    resident slide's band is its view, wherever it starts) and mapped into
+    ``out`` on the stream the read is enqueued on, so ``bands`` prefetches and
+    maps band b+1 beside the work on band b; every band pass that takes a
+    source takes this one, and every pass maps every band again."""
+
+    kind = "clahe"
+
+    def __init__(self, inner, state):
+        self.inner = as_source(inner)
+        self.H, self.W, self.C = self.inner.H, self.inner.W, self.inner.C
+        self.dtype = torch.float32
+        self.state = state
+        assert state.finished and (state.H, state.W, state.C, state.dtype) == (*self.inner.shape, self.inner.dtype), \
+            "ClaheSource: the state is not the finished equalisation of this source"
+
+    def read(self, y0, y1, out):
+        inner = self.inner
+        dst = out[:y1 - y0]
+        if inner.zero_copy:
+            raw = inner.read(y0, y1, None).contiguous()
+        elif inner.dtype == torch.float32:
+            raw = inner.read(y0, y1, dst)  # mapped in place
+        else:
+            # (allocated and released on the reading stream, as RescaleSource's)
+            raw = inner.read(y0, y1, alloc_rows(y1 - y0, (self.W, self.C), inner.dtype, min_rows=y1 - y0,
+                                                dev=out.device))
+        self.state.map(raw, y0, dst)
+        if not inner.zero_copy:
+            D.CLAHE_USED["map_streamed"] += 1
+        return dst
+
+    def mask_device(self):
+        return self.inner.mask_device()
+
+
 def pinned_empty(shape, dtype=torch.int16) -> torch.Tensor:
     """Page-locked host tensor: bands of a HostSource over it are copied by
     DMA without a staging copy."""
@@ -581,6 +628,45 @@ def quantiles(src, q, pooled: bool = False, skip_sentinel: bool = False, band_ro
     if not src.zero_copy:
         D.INTENSITY_USED["select_streamed"] += 1
     return sel.out
+
+
+def clahe(src, kernel_size, clip_limit=0.01, nbins=256, enable=None, band_rows=None, luts: bool = False):
+    """The statistics of ``device.clahe`` of a slide band after band
+    (``img.equalize_hist(banded=True)`` of a slide that is not resident, or
+    whose fp32 result may not be held): three loops over the bands through
+    mw_clahe_rows_* -- the planes' minima and maxima; the tiles' histograms,
+    then the tables; the extremes of the blend, then the rescale rows -- no
+    halo, any band height.  Every reduction is an integer one (the extremes on
+    the bits of non-negative fp32 values), so the finished state is the whole
+    slide's, bit for bit, whatever the bands.  The source is read three times
+    (a ``RescaleSource`` or ``ClaheSource`` included, whose own map runs again
+    with every read).  Returns the finished ``device.ClaheRows`` (with
+    ``luts``: and the tables) for ``ClaheSource``.  MemoryError when HBM
+    cannot hold the tables.  Nothing is synchronised."""
+    src = as_source(src)
+    H, W, C = src.shape
+    kh, kw, clip_limit, nbins = D.clahe_args(H, W, kernel_size, clip_limit, nbins)  # before any device call
+    need = D.ClaheRows.state_bytes(H, W, C, kh, kw, nbins)
+    RESIDENCY.release(need + (256 << 20))
+    have = alloc_bytes()
+    if need + (256 << 20) > have:
+        raise MemoryError(
+            f"equalize_hist(banded=True): the tables of {C} x {-(-H // kh)} x {-(-W // kw)} tiles of {nbins} bins "
+            f"take {need / 2**30:.2f} GiB and {have / 2**30:.2f} GiB can be allocated: use a larger kernel_size")
+    st = D.ClaheRows(src.dtype, H, W, C, (kh, kw), clip_limit, nbins, enable)
+    if band_rows is None:
+        band_rows = H if src.zero_copy else band_rows_for(src)
+    for _, _, _, raw in bands(src, band_rows, 0):
+        st.range(raw)
+    for y0, _, _, raw in bands(src, band_rows, 0):
+        st.hist(raw, y0)
+    tables = st.luts(out=luts)
+    for y0, _, _, raw in bands(src, band_rows, 0):
+        st.extremes(raw, y0)
+    st.finish()
+    if not src.zero_copy:
+        D.CLAHE_USED["stats_streamed"] += 1
+    return (st, tables) if luts else st
 
 
 class GaussianBand:
