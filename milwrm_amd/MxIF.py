@@ -881,7 +881,84 @@ class img:
         self._lognorm_host = None
 
     show = _out_of_scope("img.show")
-    plot_image_histogram = _out_of_scope("img.plot_image_histogram")
+
+    def histogram(self, channels=None, bins=100, range=None, mask_out=False):
+        """np.histogram of the current pixels of the planes ``channels`` (None:
+        all; indices or names, a plane listed twice comes back twice; a 2-D
+        image is one plane), each as float64 -- what ``self.img[:, :, c]``
+        holds, everything pending applied -- counted on the device (D.histogram;
+        the definition: DESIGN.md §27).  ``bins``: an int >= 1 (up to 4096);
+        ``range``: a finite (lo, hi) for every plane (elements outside are left
+        out), or None for each plane's own (nanmin, nanmax), as matplotlib's
+        ``hist`` takes it; NaNs are never counted.  ``mask_out``: only pixels
+        of the tissue mask take part, in the range too.  Returns (counts int64
+        [n, bins], edges float64 [n, bins + 1]) as host arrays.
+
+        A reader: the pixels do not change.  A slide that is not resident is
+        read band by band (stream.histogram: twice, once with a range given),
+        any pending log_normalize or deferred filter applied to each band and
+        nothing pending cleared; otherwise the pixels are materialised as
+        ``img`` does.  ValueError: ``bins`` below 1, a range that is not finite
+        or has lo > hi, a plane without an element that is not NaN or with an
+        infinite extreme (range None), ``mask_out`` without a mask."""
+        from . import stream
+
+        if getattr(self, "_band", None) is not None:
+            raise NotImplementedError("histogram of a row band of a slide split over ranks: the counts are the "
+                                      "whole slide's")
+        bins, range = D.histogram_args(bins, range)  # before any device call
+        feats = self._features(channels)
+        names = [self.ch[f] for f in feats]
+        mask = None
+        if mask_out:
+            if self._mask is None:
+                raise ValueError("histogram(mask_out=True): the image has no tissue mask")
+            mask = self._mask_device()
+        src = self._source()
+        if src is None and self._filter_deferred():
+            # a resident slide whose filter stayed deferred (its fp32 copy may not be held): filtered band by band
+            src = stream.DeviceSource(self._device())
+        if src is not None:
+            filt = stream.band_filter(self)
+            if filt is None and self._pending is not None and self._pending[0] is not None:
+                filt = stream.LogNormBand(*self._pending)
+            return stream.histogram(src, feats, bins, range, mask, filt, names=names)
+        return D.histogram(self._materialize(), feats, bins, range, mask, names=names)
+
+    def plot_image_histogram(self=None, channels=None, ncols=4, save_to=None, **kwargs):
+        """MxIF.py:733-774: one histogram of 100 bins per channel of
+        ``channels`` (indices or names) on a grid of ``ncols`` columns, drawn
+        from the device counts (``histogram``; no float64 copy of the slide).
+        ``range=`` is the histogram's as well as the drawing's, ``mask_out=``
+        the histogram's; every other keyword goes to ``Axes.hist`` (density,
+        log, color, ...).  Saves the figure to ``save_to`` if given and returns
+        the GridSpec.  ``channels`` must be given (the reference fails without
+        them too)."""
+        if self is None or channels is None:
+            raise NotImplementedError("img.plot_image_histogram: pass channels= (a list of channel indices or names) "
+                                      "to draw the device histograms")
+        import matplotlib.pyplot as plt
+        from matplotlib import gridspec
+
+        if isinstance(channels, (int, np.integer, str)):
+            channels = [channels]
+        channels = list(channels)
+        mask_out = bool(kwargs.pop("mask_out", False))
+        n = len(channels)
+        n_cols = n if n <= ncols else ncols
+        n_rows = -(-n // n_cols) if n else 1
+        fig = plt.figure(figsize=(ncols * n_cols, ncols * n_rows))
+        gs = gridspec.GridSpec(n_rows, max(n_cols, 1), figure=fig)
+        for i, channel in enumerate(channels):
+            ax = plt.subplot(gs[i])
+            counts, edges = self.histogram(channel, bins=100, range=kwargs.get("range"), mask_out=mask_out)
+            ax.hist(edges[0][:-1], bins=edges[0], weights=counts[0], **kwargs)
+            ax.set_title(channel, fontweight="bold", fontsize=16)
+        fig.tight_layout()
+        plt.show()
+        if save_to:
+            fig.savefig(save_to, dpi=300, bbox_inches="tight")
+        return gs
 
     # ------------------------------------------------------- preprocessing
     def blurring(self, filter_name="gaussian", sigma=2, **kwargs):

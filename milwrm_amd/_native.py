@@ -44,6 +44,12 @@ _PROTOS = {
     "mw_quantiles_rows_count": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mw_quantiles_rows_choose": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mw_rescale": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "mw_hist_ws_bytes": (c_sz, [c_i32, c_i32]),
+    "mw_hist_max_bins": (c_i32, []),
+    "mw_hist_rows_begin": (c_i32, [c_i32, c_i32, c_vp, c_vp]),
+    "mw_hist_rows_range": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "mw_hist_rows_count": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mw_hist_rows_finish": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mw_clahe_ws_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "mw_clahe": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, C.c_double, c_i32, c_vp, c_vp, c_vp,
                          c_vp]),

@@ -542,6 +542,175 @@ class ClaheRows:
         return out
 
 
+_range = range  # (the histogram functions take a ``range`` argument, as numpy's)
+HISTOGRAM_MAX_BINS = 4096  # mw_hist_max_bins(): one channel's table and edges in a workgroup's LDS
+# histograms taken (tests read it): of a resident tensor, or band by band from a slide that is not resident
+HISTOGRAM_USED = {"resident": 0, "streamed": 0}
+
+
+def histogram_args(bins, range=None):
+    """The arguments of a histogram checked on the host (no device call):
+    (bins, None or (lo, hi) as floats).  ValueError: ``bins`` not an int or
+    below 1, a range that is not a pair of finite numbers or has lo > hi;
+    NotImplementedError: ``bins`` above HISTOGRAM_MAX_BINS."""
+    if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)):
+        raise ValueError(f"histogram: bins must be an int >= 1 (uniform bins), got {bins!r}")
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError(f"histogram: bins must be an int >= 1, got {bins}")
+    if bins > HISTOGRAM_MAX_BINS:
+        raise NotImplementedError(f"histogram: bins {bins} (up to {HISTOGRAM_MAX_BINS})")
+    if range is None:
+        return bins, None
+    try:
+        lo, hi = (float(v) for v in range)
+    except (TypeError, ValueError):
+        raise ValueError(f"histogram: range must be a (lo, hi) pair of numbers, got {range!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"histogram: range {(lo, hi)} is not finite")
+    if lo > hi:
+        raise ValueError(f"histogram: range {(lo, hi)} has lo > hi")
+    return bins, (lo, hi)
+
+
+def histogram_edges(lo: float, hi: float, bins: int) -> np.ndarray:
+    """numpy's bin edges of ``bins`` uniform bins over (lo, hi), float64:
+    an empty range is widened by a half on either side, as np.histogram does."""
+    if lo == hi:
+        lo, hi = lo - 0.5, hi + 0.5
+    return np.linspace(lo, hi, bins + 1, dtype=np.float64)
+
+
+class HistogramRows:
+    """np.histogram of the selected planes of a slide that is handed over in
+    bands of rows (mw_hist_rows_*; stream.histogram).  With the
+    range taken from the data: ``range_rows`` every band, ``set_range()``;
+    with a given one: ``set_range((lo, hi))``.  Then ``count_rows`` every band
+    and ``finish()``.  A band is a contiguous [rows, W, C] tensor of the
+    slide's element type that may start anywhere (a view into a resident
+    slide: no 16-byte alignment is asked), ``mask_rows`` the uint8 [rows, W]
+    mask of the same rows or None: only pixels whose byte is not zero take
+    part.  ``channels``: plane indices, a plane listed twice comes back twice;
+    ``names``: what the error messages call the planes.  The counts and the
+    extremes are integer reductions, so the result is the whole slide's, bit
+    for bit, whatever the bands.  Arguments are checked on the host first
+    (``histogram_args``); ``set_range()`` and ``finish`` synchronise on the
+    few numbers they read."""
+
+    def __init__(self, dtype, C: int, channels, bins, names=None, dev=None):
+        try:
+            self.code = _DTYPE_CODE[dtype]
+        except KeyError:
+            raise TypeError(f"unsupported device image dtype {dtype}") from None
+        self.bins, _ = histogram_args(bins)
+        self.dtype, self.C = dtype, int(C)
+        self.channels = [int(c) for c in channels]
+        if not self.channels or not all(0 <= c < self.C for c in self.channels):
+            raise ValueError(f"histogram: channels {self.channels} of a {self.C}-channel image")
+        self.names = list(names) if names is not None else list(self.channels)
+        sel = sorted(set(self.channels))
+        self.rows_of = [sel.index(c) for c in self.channels]  # the table row of every requested channel
+        self.en = np.zeros(self.C, dtype=np.int32)
+        self.en[sel] = 1
+        self.n_sel = len(sel)
+        self.elem = torch.empty(0, dtype=dtype).element_size()
+        self.dev = device() if dev is None else dev
+        self.edges = self.d_edges = None
+        nbytes = N.query("mw_hist_ws_bytes", self.C, self.bins)
+        if nbytes == 0:
+            raise NotImplementedError(f"histogram: {self.C} channels, {self.bins} bins (up to 256 channels, "
+                                      f"{HISTOGRAM_MAX_BINS} bins)")
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        N.call("mw_hist_rows_begin", self.C, self.bins, P(self.state), stream())
+
+    def _band(self, rows, mask_rows) -> int:
+        if rows.dtype != self.dtype or rows.dim() != 3 or int(rows.shape[2]) != self.C:
+            raise ValueError(f"histogram: a band must be [rows, W, {self.C}] of {self.dtype}, got "
+                             f"{tuple(rows.shape)} of {rows.dtype}")
+        if not rows.is_contiguous():
+            raise ValueError("histogram: the band must be contiguous")
+        if mask_rows is not None and (mask_rows.dtype != torch.uint8 or tuple(mask_rows.shape) != tuple(rows.shape[:2])
+                                      or not mask_rows.is_contiguous()):
+            raise ValueError(f"histogram: the band's mask must be a contiguous uint8 {tuple(rows.shape[:2])} tensor")
+        return int(rows.shape[0]) * int(rows.shape[1])
+
+    def range_rows(self, rows: torch.Tensor, mask_rows=None):
+        """Fold a band into the planes' extremes (every band once)."""
+        n_pix = self._band(rows, mask_rows)
+        if n_pix == 0:
+            return
+        with profiling.timed("hist_range", n_pix * self.C * self.elem):
+            N.call("mw_hist_rows_range", P(rows), self.code, n_pix, self.C, self.en.ctypes.data, self.bins,
+                   P(mask_rows), P(self.state), stream())
+
+    def set_range(self, range=None) -> np.ndarray:
+        """Make the edges and upload them: np.linspace over ``range`` for
+        every plane, or (None, after the last ``range_rows``) over each
+        plane's own (nanmin, nanmax).  ValueError naming the plane when it
+        holds no element that is not NaN, or an infinite one.  Returns the
+        float64 [n requested, bins + 1] edges."""
+        if range is not None:
+            _, (lo, hi) = histogram_args(self.bins, range)
+            table = np.tile(histogram_edges(lo, hi, self.bins), (self.n_sel, 1))
+        else:
+            rec = torch.empty((self.n_sel, 4), dtype=torch.float64, device=self.dev)
+            N.call("mw_hist_rows_finish", self.code, self.C, self.en.ctypes.data, self.bins, None, P(rec),
+                   P(self.state), stream())
+            rec = d2h(rec)
+            table = np.empty((self.n_sel, self.bins + 1), dtype=np.float64)
+            for name, r in zip(self.names, self.rows_of):
+                lo, hi, n = rec[r, 0], rec[r, 1], rec[r, 2]
+                if n == 0:
+                    raise ValueError(f"histogram: channel {name!r} holds no element that is not NaN")
+                if not (np.isfinite(lo) and np.isfinite(hi)):
+                    raise ValueError(f"histogram: channel {name!r} has the infinite range {(float(lo), float(hi))}")
+                table[r] = histogram_edges(float(lo), float(hi), self.bins)
+        self.edges = table[self.rows_of]
+        self.d_edges = h2d(table, self.dev)
+        return self.edges
+
+    def count_rows(self, rows: torch.Tensor, mask_rows=None):
+        """Add a band to the counts (every band once, after ``set_range``)."""
+        if self.d_edges is None:
+            raise ValueError("histogram: count_rows before set_range")
+        n_pix = self._band(rows, mask_rows)
+        if n_pix == 0:
+            return
+        with profiling.timed("hist_count", n_pix * self.C * self.elem):
+            N.call("mw_hist_rows_count", P(rows), self.code, n_pix, self.C, self.en.ctypes.data, self.bins,
+                   P(self.d_edges), P(mask_rows), P(self.state), stream())
+
+    def finish(self):
+        """(counts int64 [n requested, bins], edges float64 [n requested,
+        bins + 1]) as host arrays, in the order of ``channels``."""
+        if self.d_edges is None:
+            raise ValueError("histogram: finish before set_range")
+        counts = torch.empty((self.n_sel, self.bins), dtype=torch.int64, device=self.dev)
+        N.call("mw_hist_rows_finish", self.code, self.C, self.en.ctypes.data, self.bins, P(counts), None,
+               P(self.state), stream())
+        return d2h(counts)[self.rows_of], self.edges.copy()
+
+
+def histogram(t: torch.Tensor, channels=None, bins=100, range=None, mask=None, names=None):
+    """np.histogram of the planes ``channels`` (indices; None: all) of a
+    resident HWC tensor, each as float64: (counts int64 [n, bins], edges
+    float64 [n, bins + 1]) on the host.  ``range`` None: each plane's own
+    (nanmin, nanmax), as matplotlib's ``hist`` passes it.  ``mask``: uint8
+    [H, W], only pixels whose byte is not zero take part.  The one-band case of
+    ``HistogramRows``: the tensor is read twice, once when a range is given."""
+    H, W, C = t.shape
+    bins, range = histogram_args(bins, range)  # before any device call
+    if not t.is_contiguous():
+        raise ValueError("histogram: the image must be contiguous")
+    st = HistogramRows(t.dtype, C, list(_range(C)) if channels is None else channels, bins, names, t.device)
+    if range is None:
+        st.range_rows(t, mask)
+    st.set_range(range)
+    st.count_rows(t, mask)
+    HISTOGRAM_USED["resident"] += 1
+    return st.finish()
+
+
 def gaussian_taps(sigma: float, truncate: float = 4.0) -> np.ndarray:
     """scipy ``_gaussian_kernel1d`` order 0 (radius int(truncate*sigma+0.5)),
     computed in fp64 then rounded to fp32 for the kernel."""

@@ -811,6 +811,48 @@ def downsample(src, fact: int, func=np.mean, filt=None) -> torch.Tensor:
     return out
 
 
+def histogram(src, channels=None, bins=100, range=None, mask=None, filt=None, band_rows=None, names=None):
+    """``device.histogram`` of a slide band after band (``img.histogram`` of a
+    slide that is not resident): np.histogram of the planes ``channels``
+    (indices; None: all) as float64, (counts int64 [n, bins], edges float64
+    [n, bins + 1]) on the host.  ``filt``: a band filter applied to the rows
+    first (a deferred Gaussian, median or bilateral, or ``LogNormBand``), as
+    ``downsample`` takes it.  ``mask``: device uint8 [H, W], only pixels whose
+    byte is not zero take part.  The source is read twice with ``range`` None
+    (the planes' extremes, then the counts: mw_hist_rows_range / _count), once
+    with a range given; a filter's halo rows are read again with every band.
+    Every reduction is an integer one, so the result is the resident slide's,
+    bit for bit, whatever the bands."""
+    src = as_source(src)
+    bins, range = D.histogram_args(bins, range)  # before any device call
+    H, W, C = src.shape
+    st = D.HistogramRows(src.dtype if filt is None else torch.float32, C,
+                         list(np.arange(C)) if channels is None else channels, bins, names)
+    if band_rows is None:
+        band_rows = H if src.zero_copy and filt is None else band_rows_for(src, 0 if filt is None else W * C * 4)
+    buf = None
+    if filt is not None:
+        want = min(H, band_rows + 2 * filt.halo)
+        buf = alloc_rows(want, (W, C), torch.float32, min_rows=min(want, 1 + 2 * filt.halo))
+        if int(buf.shape[0]) < want:  # HBM was short: lower bands
+            band_rows = max(1, int(buf.shape[0]) - 2 * filt.halo)
+
+    def each(take):
+        if filt is None:
+            for y0, y1, _, raw in bands(src, band_rows, 0):
+                take(raw, None if mask is None else mask[y0:y1])
+        else:
+            for y0, y1, core in filtered_bands(src, filt, band_rows, buf):
+                take(core, None if mask is None else mask[y0:y1])
+
+    if range is None:
+        each(st.range_rows)
+    st.set_range(range)
+    each(st.count_rows)
+    D.HISTOGRAM_USED["resident" if src.zero_copy else "streamed"] += 1
+    return st.finish()
+
+
 def _band_gather(src, filt, feat: torch.Tensor, idx: torch.Tensor, r2p, X_out: torch.Tensor, band_rows,
                  fused=None) -> bool:
     """X_out[j] = filtered slide[pixel of rank idx[j], feat]: the sample map
